@@ -26,7 +26,11 @@ scaling).  The step is the SAME strategy code the entry scripts run (parallel/st
 The full training step (preprocess, forward, backward, all-reduce, optimizer, weight re-prep)
 is inside the timed region: W untimed warmup steps, then K timed steps bracketed by a barrier
 + device synchronize on both sides; the MAX time over ranks is reported.  Rank 0 prints ONE
-JSON line; `value` is the whole-job aggregate images/sec.
+JSON line; `value` is the whole-job aggregate images/sec and `ms_per_step` the milliseconds one
+of the K timed steps took.  A plain run does only that: set up, warm up, time, report.
+--dump-outputs DIR adds DIR/stats.npy, grads.npy, params.npy of one more, untimed step of the
+same path from the seeded state (see dump_outputs for why not the last timed step's); --full
+is where measurements beyond the headline figure go (none today).
 
 Launch checks: with --gpus N > 1 and no torchrun environment the parent spawns the rank
 processes (or runs the in-process Mirrored path) before anything touches the GPU, and exits
@@ -105,6 +109,15 @@ def parse(argv=None):
     ap.add_argument("--timeout", type=float, default=None,
                     help="job deadline in seconds (default: derived from steps + warmup); on expiry every "
                          "rank dumps its stacks and the job exits non-zero")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps run the timed step once more from the seeded parameters and "
+                         "optimizer state and write what it computed as DIR/<name>.npy (rank 0's first replica: "
+                         "stats, and seeded samples of the gradients and the updated parameters); inputs and "
+                         "state depend on the arguments only, so two builds compare output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond the headline figure; a plain run sets "
+                         "up, warms up, times the steps and reports (today the headline run is all there is, so "
+                         "the two print the same line)")
     args = ap.parse_args(argv)
     if args.batch is None:
         # (train-mode BN keeps every pre-BN activation: at 2560 they pass the kernels' 2^31-element
@@ -328,6 +341,7 @@ def run(args):
             dist.barrier()
         sync_all()
 
+    seeded = snapshot_state(st) if args.dump_outputs else None
     stats = None
     for i in range(args.warmup):
         progress("warmup", i)
@@ -348,6 +362,14 @@ def run(args):
             t = t.cuda()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if seeded is not None:
+        # (every rank: the dumped step runs the same collectives as a timed one)
+        progress("dump step")
+        restore_state(st, seeded)
+        dumped = st.train_step(images, labels)
+        barrier()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dumped, next(iter(st._replicas()))[0])
     loss = float(stats[0].item()) / (B * len(local_devs)) if stats is not None else float("nan")
     comm = comm_report(st, world, rank, local_devs, cpu)
     total = B * args.gpus
@@ -406,6 +428,51 @@ def run(args):
         dist.destroy_process_group()
     faulthandler.cancel_dump_traceback_later()
     return 0
+
+
+DUMP_SAMPLE = 4 << 20     # elements kept of each large output (16 MiB as float32)
+DUMP_SEED = 20240
+
+
+def snapshot_state(st):
+    """Parameters, optimizer slots and step count of every local replica, as seeded."""
+    return [(e.params.clone(), {k: t.clone() for k, t in o.state_tensors().items()}, o.iterations)
+            for e, o in st._replicas()]
+
+
+def restore_state(st, snap):
+    for (e, o), (params, slots, it) in zip(st._replicas(), snap):
+        e.params.copy_(params)
+        for k, t in o.state_tensors().items():
+            t.copy_(slots[k])
+        o.iterations = it
+        e.after_update()
+
+
+def dump_outputs(path, stats, engine):
+    """--dump-outputs: what a caller of the timed step holds after one step -- `stats` (loss
+    sum, correct count: what train_step returned) in float64, and the step's gradients and
+    updated parameters in float32.  A flat tensor longer than DUMP_SAMPLE is cut to the same
+    sorted sample of positions in every run (numpy default_rng(DUMP_SEED)); the whole dump
+    stays under 64 MB.
+
+    The step written is one more call of the timed step, on the timed batch, made after the
+    timed region from the seeded parameters and optimizer state (run(): snapshot_state /
+    restore_state).  The last timed step itself does not repeat from run to run: the fp32
+    atomics of the weight-gradient kernels add in no fixed order, and W + K Adam steps from a
+    random initialisation amplify that rounding (tests/test_gpu_engine.py, loss trajectory) to
+    1e-4 of the loss and more of single parameters.  One step from the seeded state differs
+    between runs by the atomics' rounding alone, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stats.npy"), stats.detach().to("cpu").double().numpy())
+    for name, t in (("grads", engine.grads), ("params", engine.params)):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=DUMP_SAMPLE))
+            import torch
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, f"{name}.npy"), flat.to("cpu").float().numpy())
 
 
 def add_scaling(out, args):
@@ -537,6 +604,9 @@ def main(argv=None):
     if args.strategy == "ps":
         if "WORLD_SIZE" in os.environ:
             fail("--strategy ps spawns its own P + W role processes; do not launch it with torchrun")
+        if args.dump_outputs:
+            fail("--dump-outputs: the asynchronous parameter-server job has no step whose outputs repeat "
+                 "from run to run")
         return run_ps(args)
     torchrun = "WORLD_SIZE" in os.environ
     if not torchrun and args.gpus > 1 and args.strategy != "mirrored":

@@ -25,9 +25,10 @@ def build(verbose: bool = False) -> str:
     env = dict(os.environ)
     env.setdefault("PDDL_OFFLOAD_ARCH", "gfx950")
     env.setdefault("MAX_JOBS", "8")
-    # object files stay outside the tree so GPU-box snapshots only carry the .so files
-    cmd = [sys.executable, "setup.py", "build_ext", "--inplace", "--build-temp",
-           os.path.join(os.environ.get("TMPDIR", "/tmp"), "pddl_build_temp")]
+    # object files stay outside the tree so GPU-box snapshots only carry the .so files; one
+    # directory per user, so a build never meets objects it may not overwrite
+    env.setdefault("PDDL_BUILD_TEMP", os.path.join(os.environ.get("TMPDIR", "/tmp"), f"pddl_build_temp_{os.getuid()}"))
+    cmd = [sys.executable, "setup.py", "build_ext", "--inplace", "--build-temp", env["PDDL_BUILD_TEMP"]]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=not verbose, text=True)
     shutil.rmtree(os.path.join(ROOT, "build"), ignore_errors=True)
     if r.returncode != 0:

@@ -99,6 +99,35 @@ def test_bench_baseline_ips_fills_efficiency():
     assert "scaling_efficiency" not in _json(_bench(*SMALL))
 
 
+def test_dump_outputs_repeat_and_steps_are_timed(tmp_path):
+    """--dump-outputs DIR: stats / grads / params of one step of the timed path from the seeded
+    state as float .npy files under 64 MB, identical from run to run with the same arguments
+    (the CPU engine is deterministic);
+    --steps is the number of timed steps and ms_per_step is the time of one of them; --full
+    accepts the same run."""
+    import numpy as np
+    outs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = _bench("--device", "cpu", "--steps", "2", "--warmup", "1", "--batch", "2", "--image-size", "32",
+                   "--dump-outputs", str(d), *extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = _json(r)
+        assert out["steps"] == 2 and out["warmup"] == 1
+        assert out["value"] == pytest.approx(2 * 1e3 / out["ms_per_step"], rel=1e-3)
+        files = sorted(os.listdir(d))
+        assert files == ["grads.npy", "params.npy", "stats.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64e6
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        # (loss sum, correct count) of one step from the seeded state on the batch of 2
+        assert arrs["stats.npy"].shape == (2,) and arrs["stats.npy"][0] > 0 and 0 <= arrs["stats.npy"][1] <= 2
+        assert np.abs(arrs["grads.npy"]).max() > 0
+        outs.append(arrs)
+    for f in outs[0]:
+        assert np.array_equal(outs[0][f], outs[1][f]), f
+
+
 def test_bench_scaling_script_cpu():
     """bench/scaling.py: fresh bench.py children at N = 1 and 2 (gloo CPU ranks under
     torch.distributed.run), per-N rows, efficiency 1.0 at N = 1, JSON summary schema."""
