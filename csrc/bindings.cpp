@@ -69,11 +69,10 @@ int64_t splitk_default_floats(int64_t device) {   // the heuristic's bound: tile
 }
 
 // Generic implicit-GEMM (conv forward / dgrad / fp32 dense).
-void igemm_impl(Tensor a1, OptT a2, int64_t H, int64_t W, int64_t R, int64_t S, int64_t stride, int64_t pad,
-                int64_t Ho, int64_t Wo, Tensor b, int64_t mode, OptT scale, OptT shift, OptT res, OptT mask,
-                OptT add, Tensor out, int64_t relu, OptT out2, int64_t relu2, int64_t n_split, int64_t up2,
-                int64_t Hf, int64_t Wf, OptT colsum, OptT bits_out, OptT stats, OptT bn_z = c10::nullopt,
-                OptT bn_mean = c10::nullopt) {
+void igemm(Tensor a1, OptT a2, int64_t H, int64_t W, int64_t R, int64_t S, int64_t stride, int64_t pad,
+           int64_t Ho, int64_t Wo, Tensor b, int64_t mode, OptT scale, OptT shift, OptT res, OptT mask,
+           OptT add, Tensor out, int64_t relu, OptT out2, int64_t relu2, int64_t n_split, int64_t up2,
+           int64_t Hf, int64_t Wf, OptT colsum, OptT bits_out, OptT stats, OptT bn_z, OptT bn_mean) {
   pddl::IgemmParams p{};
   PCHECK(a1.is_contiguous(), "A source must be contiguous NHWC");
   p.a1 = bfp(a1);
@@ -174,14 +173,6 @@ void igemm_impl(Tensor a1, OptT a2, int64_t H, int64_t W, int64_t R, int64_t S, 
     p.slab_floats = tls_splitk.numel();
   }
   ok(pddl::igemm_launch(p, cur_stream()), "igemm");
-}
-
-void igemm(Tensor a1, OptT a2, int64_t H, int64_t W, int64_t R, int64_t S, int64_t stride, int64_t pad,
-           int64_t Ho, int64_t Wo, Tensor b, int64_t mode, OptT scale, OptT shift, OptT res, OptT mask, OptT add,
-           Tensor out, int64_t relu, OptT out2, int64_t relu2, int64_t n_split, int64_t up2, int64_t Hf,
-           int64_t Wf, OptT colsum, OptT bits_out) {
-  igemm_impl(a1, a2, H, W, R, S, stride, pad, Ho, Wo, b, mode, scale, shift, res, mask, add, out, relu, out2, relu2,
-             n_split, up2, Hf, Wf, colsum, bits_out, c10::nullopt);
 }
 
 // ---- train-mode BatchNormalization (bn.hip)
@@ -823,21 +814,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     ok(pddl::comm_proxy_launch(f32p(src), f32p(scratch), src.numel(), passes, ticks, nch, cur_stream()),
        "comm_proxy");
   }, REL);
-  m.def("igemm", &igemm, REL);
-  m.def("igemm_bn", &igemm_impl, REL);
+  // (argument order is part of the interface: tests, bench/ and scripts/ call these positionally.
+  // An optional argument in the middle keeps its default; the required ones after it are then
+  // passed by keyword.)
+  const py::none none;
+  m.def("igemm", &igemm, REL, py::arg("a1"), py::arg("a2") = none, py::arg("H"), py::arg("W"), py::arg("R"),
+        py::arg("S"), py::arg("stride"), py::arg("pad"), py::arg("Ho"), py::arg("Wo"), py::arg("b"), py::arg("mode"),
+        py::arg("scale") = none, py::arg("shift") = none, py::arg("res") = none, py::arg("mask") = none,
+        py::arg("add") = none, py::arg("out"), py::arg("relu") = 0, py::arg("out2") = none, py::arg("relu2") = 0,
+        py::arg("n_split") = 0, py::arg("up2") = 0, py::arg("Hf") = 0, py::arg("Wf") = 0, py::arg("colsum") = none,
+        py::arg("bits_out") = none, py::arg("stats") = none, py::arg("bn_z") = none, py::arg("bn_mean") = none);
   m.def("bn_stats", &bn_stats, REL);
-  m.def("bn_apply", &bn_apply, REL);
-  m.def("bn_bwd_reduce", &bn_bwd_reduce, REL);
-  m.def("bn_bwd_apply", &bn_bwd_apply, REL);
+  m.def("bn_apply", &bn_apply, REL, py::arg("z"), py::arg("a"), py::arg("b"), py::arg("r") = none,
+        py::arg("a2") = none, py::arg("b2") = none, py::arg("relu"), py::arg("y"), py::arg("bits") = none);
+  m.def("bn_bwd_reduce", &bn_bwd_reduce, REL, py::arg("g"), py::arg("z"), py::arg("z2") = none, py::arg("mean"),
+        py::arg("mean2") = none, py::arg("sg"), py::arg("sgx"), py::arg("sg2") = none, py::arg("sgx2") = none);
+  m.def("bn_bwd_apply", &bn_bwd_apply, REL, py::arg("g"), py::arg("z"), py::arg("z2") = none, py::arg("l"),
+        py::arg("l2") = std::vector<double>{}, py::arg("params"), py::arg("mean"), py::arg("inv"), py::arg("sg"),
+        py::arg("sgx"), py::arg("dz"), py::arg("dz2") = none, py::arg("grads"), py::arg("coef"));
   m.attr("BNSTAT_LAYER_BYTES") = (int)sizeof(pddl::BnStatLayer);
-  m.def("wgrad", &wgrad, REL);
+  m.def("wgrad", &wgrad, REL, py::arg("x"), py::arg("H"), py::arg("W"), py::arg("R"), py::arg("S"),
+        py::arg("stride"), py::arg("pad"), py::arg("Ho"), py::arg("Wo"), py::arg("g"), py::arg("g2") = none,
+        py::arg("co_split") = 0, py::arg("dw"), py::arg("K"), py::arg("splits") = 0);
   m.def("bwd1x1", &bwd1x1, REL, py::arg("g"), py::arg("x"), py::arg("wd"), py::arg("bits"), py::arg("out"),
         py::arg("colsum"), py::arg("dw"), py::arg("out2") = py::none(), py::arg("g1") = py::none(),
         py::arg("w1d") = py::none(), py::arg("gmask") = py::none(), py::arg("gx") = py::none(),
         py::arg("colsum_gx") = py::none());
   m.def("bwd1x1_partial_rows", &bwd1x1_partial_rows);
   m.def("conv_f32", &conv_f32, REL);
-  m.def("conv_f32_epi", &conv_f32_epi, REL);
+  m.def("conv_f32_epi", &conv_f32_epi, REL, py::arg("x"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("Ho"), py::arg("Wo"), py::arg("w"), py::arg("epi"), py::arg("scale") = none,
+        py::arg("shift") = none, py::arg("res") = none, py::arg("relu") = 0, py::arg("add") = none,
+        py::arg("mask") = none, py::arg("up2") = 0, py::arg("y"), py::arg("colsum") = none);
   m.def("maxpool_fwd_f32", &maxpool_fwd_f32, REL);
   m.def("maxpool_bwd_f32", &maxpool_bwd_f32, REL);
   m.def("gap_fwd_f32", &gap_fwd_f32, REL);

@@ -39,6 +39,9 @@ _CRED_FMT = "<q4i"
 _BNG_FMT = "<9i"
 _FUSE_FMT = "<16iq"   # FuseLayer (csrc/kernels/kernels.h)
 E = "PDDL_ENGINE"     # the engine's fusion / schedule switches (utils/envopts.py KEYS)
+# igemm epilogue modes (EpiMode, csrc/kernels/kernels.h; checked against the extension's EPI_*).
+# (engine_f32.py numbers its own EPI_* differently: those belong to conv_f32_epi.)
+IGEMM_FWD, IGEMM_DGRAD, IGEMM_F32 = 0, 1, 2
 
 
 def _ceil(a, b):
@@ -110,6 +113,7 @@ class HipEngine:
         assert struct.calcsize(_BNG_FMT) == self.N.BNGRAD_LAYER_BYTES
         assert struct.calcsize(_FUSE_FMT) == self.N.FUSE_LAYER_BYTES
         assert struct.calcsize(_CRED_FMT) == self.N.COLRED_LAYER_BYTES
+        assert (IGEMM_FWD, IGEMM_DGRAD, IGEMM_F32) == (self.N.EPI_FWD, self.N.EPI_DGRAD, self.N.EPI_F32)
         dev = self.device
         L = layout
         self.params = torch.zeros(L.total, dtype=torch.float32, device=dev)
@@ -500,13 +504,12 @@ class HipEngine:
         return (bool(self.c3c1) and nb is not None and b.filters == 64 and nb.filters == 64 and not b.proj
                 and not nb.proj and nb.stride == 1)
 
-    def _c2_wgrad(self, W, y1, g2, c2n, f, B, Ho, g2_n):
+    def _c2_wgrad(self, y1, g2, c2n, f, B, Ho, g2_n):
         """Weight gradient of a bottleneck's stride-1 3x3 conv (on the side stream when two-stream)."""
         if self.c64w and self._use_c64(f, B * Ho * Ho, Ho) and Ho + 2 <= 64:
-            W(self.N.conv3x3c64_wgrad, y1, g2, self._gview(c2n, f, 9 * f), reads=(g2_n,))
+            self._side_run(self.N.conv3x3c64_wgrad, y1, g2, self._gview(c2n, f, 9 * f), reads=(g2_n,))
         else:
-            W(self.N.wgrad, y1, Ho, Ho, 3, 3, 1, 1, Ho, Ho, g2, None, 0, self._gview(c2n, f, 9 * f), 9 * f, 0,
-              reads=(g2_n,))
+            self._wgrad(y1, g2, self._gview(c2n, f, 9 * f), Ho, Ho, k=3, pad=1, reads=(g2_n,))
 
     def _wdv(self, name, cin, k):
         o = self.wd[name]
@@ -515,6 +518,29 @@ class HipEngine:
     def _gview(self, name, rows, k):
         o = self.L.off(name, "kernel")
         return self.grads[o:o + rows * k].view(rows, k)
+
+    # ------------------------------------------------------------------ conv launches
+    # (the two places that know the bindings' argument order; square geometry: H x H input, k x k taps, Ho x Ho output)
+    def _igemm(self, x, w, out, H, Ho, *, k=1, stride=1, pad=0, x2=None, mode=IGEMM_FWD, ch=None, res=None,
+               mask=None, add=None, relu=0, out2=None, relu2=0, n_split=0, up2=0, Hf=0, colsum=None, bits=None,
+               stats=None, bn_z=None, bn_mean=None):
+        """out = epilogue(conv([x | x2], w)): x [B,H,H,C] (x2: second K source), w [Nn][>=K] rows.
+        ch: channel offset of the layer's folded scale / shift (forward epilogues); Hf: the finer
+        grid of an up2 scatter / stride-2 residual."""
+        scale, shift = (None, None) if ch is None else (self.scale[ch:], self.shift[ch:])
+        self.N.igemm(x, x2, H, H, k, k, stride, pad, Ho, Ho, w, mode, scale, shift, res, mask, add, out, relu, out2,
+                     relu2, n_split, up2, Hf, Hf, colsum, bits, stats, bn_z, bn_mean)
+
+    def _wgrad(self, x, g, dw, H, Ho, *, k=1, stride=1, pad=0, g2=None, co_split=0, K=None, splits=0, reads=(),
+               side=True):
+        """dw [Cout][>=K] += g^T . im2col(x) through _side_run (side=False: on the calling stream);
+        g2 / co_split: a second gradient for the rows from co_split on; K defaults to dw's width."""
+        fn = self.N.wgrad
+        args = (x, H, H, k, k, stride, pad, Ho, Ho, g, g2, co_split, dw, dw.shape[1] if K is None else K, splits)
+        if side:
+            self._side_run(fn, *args, reads=reads)
+        else:
+            fn(*args)
 
     # ------------------------------------------------------------------ forward
     def _stem_mode(self, training, crop_offset):
@@ -543,9 +569,7 @@ class HipEngine:
                             pool, self.pidx[:B], self.pool_bits[:B] if use_bits else None)
         else:
             c1 = self.c1[:B]
-            N.igemm(x2, None, Hs, Hs, 4, 4, 1, 0, H1, H1, self._wf(s.name, 64, STEM_K), 0,
-                    self.scale[chs:], self.shift[chs:], None, None, None, c1, 1,
-                    None, 0, 0, 0, 0, 0, None, None)
+            self._igemm(x2, self._wf(s.name, 64, STEM_K), c1, Hs, H1, k=4, ch=chs, relu=1)
             N.maxpool_fwd(c1, pool, self.pidx[:B], self.pool_bits[:B] if use_bits else None)
         x = pool
         c1_done = False   # this block's conv1 already ran inside the previous block's c3c1 launch
@@ -564,28 +588,22 @@ class HipEngine:
                 # conv1 alone; the shortcut conv runs inside conv3's GEMM (second A source = the block
                 # input at the block's stride, K = f + cin, both BN scales folded into the weights), so
                 # the shortcut activation is never written and re-read as a residual
-                N.igemm(x, None, Hx, Hx, 1, 1, sx, 0, Ho, Ho, self._wf(c1n, f, cin), 0,
-                        self.scale[ch1:], self.shift[ch1:], None, None, None, y1, 1, None, 0, 0, 0, 0, 0, None,
-                        bt.get("y1"))
+                self._igemm(x, self._wf(c1n, f, cin), y1, Hx, Ho, stride=sx, ch=ch1, relu=1, bits=bt.get("y1"))
                 res = None
             elif b.proj:
-                N.igemm(x, None, Hx, Hx, 1, 1, sx, 0, Ho, Ho, self._wf(c1n, 5 * f, cin), 0,
-                        self.scale[ch1:], self.shift[ch1:], None, None, None, y1, 1, a["sc"][:B], 0, f, 0, 0, 0,
-                        None, bt.get("y1"))
+                self._igemm(x, self._wf(c1n, 5 * f, cin), y1, Hx, Ho, stride=sx, ch=ch1, relu=1, out2=a["sc"][:B],
+                            n_split=f, bits=bt.get("y1"))
                 res = a["sc"][:B]
             else:
-                N.igemm(x, None, H, H, 1, 1, 1, 0, Ho, Ho, self._wf(c1n, f, cin), 0,
-                        self.scale[ch1:], self.shift[ch1:], None, None, None, y1, 1, None, 0, 0, 0, 0, 0, None,
-                        bt.get("y1"))
+                self._igemm(x, self._wf(c1n, f, cin), y1, H, Ho, ch=ch1, relu=1, bits=bt.get("y1"))
                 res = x
             c2 = b.convs["2"].name
             if self._use_c64(f, B * Ho * Ho, Ho):
                 N.conv3x3c64(y1, self._wf(c2, f, 9 * f), 0, y2, scale=self.scale[self.ch[c2]:],
                              shift=self.shift[self.ch[c2]:], bits=bt.get("y2"))
             else:
-                N.igemm(y1, None, Ho, Ho, 3, 3, 1, 1, Ho, Ho, self._wf(c2, f, 9 * f), 0,
-                        self.scale[self.ch[c2]:], self.shift[self.ch[c2]:], None, None, None, y2, 1, None, 0, 0, 0,
-                        0, 0, None, bt.get("y2"))
+                self._igemm(y1, self._wf(c2, f, 9 * f), y2, Ho, Ho, k=3, pad=1, ch=self.ch[c2], relu=1,
+                            bits=bt.get("y2"))
             c3 = b.convs["3"].name
             nb = L.blocks[bi + 1] if bi + 1 < len(L.blocks) else None
             c1_done = False
@@ -602,28 +620,36 @@ class HipEngine:
                 c1_done = True
             elif b.proj and self.fuse_proj:
                 fz = "fuse:" + b.name
-                N.igemm(y2, x, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wf(fz, 4 * f, f + cin), 0,
-                        self.scale[self.ch[fz]:], self.shift[self.ch[fz]:], None, None, None, out, 1, None, 0, 0, 0,
-                        0, 0, None, bt.get("out"))
+                self._igemm(y2, self._wf(fz, 4 * f, f + cin), out, Ho, Ho, x2=x, ch=self.ch[fz], relu=1,
+                            bits=bt.get("out"))
             elif self._out_dim(bi, Ho) != Ho:
                 # feeds a downsampling block: conv3 on the stride-2 grid only (1x1 stride-2 gather
                 # of y2, residual read at the grid positions of the full-resolution block input)
                 Hq = self._out_dim(bi, Ho)
-                N.igemm(y2, None, Ho, Ho, 1, 1, 2, 0, Hq, Hq, self._wf(c3, 4 * f, f), 0,
-                        self.scale[self.ch[c3]:], self.shift[self.ch[c3]:], res, None, None, out, 1, None, 0, 0, 1,
-                        Ho, Ho, None, bt.get("out"))
+                self._igemm(y2, self._wf(c3, 4 * f, f), out, Ho, Hq, stride=2, ch=self.ch[c3], res=res, relu=1,
+                            up2=1, Hf=Ho, bits=bt.get("out"))
             else:
-                N.igemm(y2, None, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wf(c3, 4 * f, f), 0,
-                        self.scale[self.ch[c3]:], self.shift[self.ch[c3]:], res, None, None, out, 1, None, 0, 0, 0,
-                        0, 0, None, bt.get("out"))
+                self._igemm(y2, self._wf(c3, 4 * f, f), out, Ho, Ho, ch=self.ch[c3], res=res, relu=1,
+                            bits=bt.get("out"))
             x = out
         pooled = self.pooled[:B]
         N.gap_fwd(x, pooled)
-        logits = self.logits[:B]
-        chd = self.ch["dense"]
-        N.igemm(pooled.view(B, 1, 1, 2048), None, 1, 1, 1, 1, 1, 0, 1, 1, self._wf("dense", self.num_classes, 2048), 2,
-                self.scale[chd:], self.shift[chd:], None, None, None, logits, 0, None, 0, 0, 0, 0, 0, None, None)
+        self._dense_fwd(pooled, B)
         return x
+
+    def _dense_fwd(self, pooled, B):
+        """logits (fp32) = pooled . W^T + bias."""
+        self._igemm(pooled.view(B, 1, 1, 2048), self._wf("dense", self.num_classes, 2048), self.logits[:B], 1, 1,
+                    mode=IGEMM_F32, ch=self.ch["dense"])
+
+    def _dense_bwd(self, pooled, dl, B, *, side=True):
+        """Dense head backward: weight gradient, bias column sums, data gradient -> dpooled."""
+        self._wgrad(pooled.view(B, 1, 1, 2048), dl, self._gview("dense", self.num_classes, 2048), 1, 1, side=side)
+        self.N.colsum(dl, self.num_classes, self.colsum[self.ch["dense"]:])
+        dpooled = self.dpooled[:B]
+        self._igemm(dl.view(B, 1, 1, self.ncls_pad), self._wdv("dense", 2048, self.ncls_pad), dpooled, 1, 1,
+                    mode=IGEMM_DGRAD)
+        return dpooled
 
     def _labels(self, labels, B):
         lab = self.labels_dev[:B]
@@ -765,15 +791,7 @@ class HipEngine:
                 nb[0] += 1
 
         # ---- head
-        pooled = self.pooled[:B]
-        chd = self.ch["dense"]
-        W(N.wgrad, pooled.view(B, 1, 1, 2048), 1, 1, 1, 1, 1, 0, 1, 1, dl, None, 0,
-          self._gview("dense", self.num_classes, 2048), 2048, 0)
-        N.colsum(dl, self.num_classes, self.colsum[chd:])
-        dpooled = self.dpooled[:B]
-        N.igemm(dl.view(B, 1, 1, self.ncls_pad), None, 1, 1, 1, 1, 1, 0, 1, 1,
-                self._wdv("dense", 2048, self.ncls_pad), 1, None, None, None, None, None, dpooled, 0,
-                None, 0, 0, 0, 0, 0, None, None)
+        dpooled = self._dense_bwd(self.pooled[:B], dl, B)
         e = L.entry("dense", "kernel")
         done_upto(e.offset + e.size)
         cur = 0
@@ -823,13 +841,11 @@ class HipEngine:
                     self._before_write(g2_n, "g2c")
                     N.bwd1x1(gc, y2, self._wdv(c3n, f, 4 * f), y2m, g2, part(c2n), self._gview(c3n, 4 * f, f), g2c)
                 else:
-                    W(N.wgrad, y2, Ho, Ho, 1, 1, 2, 0, Hc, Hc, gc, None, 0, self._gview(c3n, 4 * f, f), f, 0,
-                      reads=("gc",))
+                    self._wgrad(y2, gc, self._gview(c3n, 4 * f, f), Ho, Hc, stride=2, reads=("gc",))
                     self._before_write(g2_n, "g2c")
-                    N.igemm(gc, None, Hc, Hc, 1, 1, 1, 0, Hc, Hc, self._wdv(c3n, f, 4 * f), 1, None, None, None, y2m,
-                            None, g2, 0, g2c, 0, 0, 2, Ho, Ho, part(c2n), None)
-                W(N.wgrad, y1, Ho, Ho, 3, 3, 2, 1, Hc, Hc, g2c, None, 0, self._gview(c2n, f, 9 * f), 9 * f, 0,
-                  reads=("g2c",))
+                    self._igemm(gc, self._wdv(c3n, f, 4 * f), g2, Hc, Hc, mode=IGEMM_DGRAD, mask=y2m, out2=g2c,
+                                up2=2, Hf=Ho, colsum=part(c2n))
+                self._wgrad(y1, g2c, self._gview(c2n, f, 9 * f), Ho, Hc, k=3, stride=2, pad=1, reads=("g2c",))
             elif self._bwd_fused(bi, b, s2):
                 # conv3: data and weight gradient from one read of gout
                 self._before_write(g2_n)
@@ -840,31 +856,30 @@ class HipEngine:
                              g1=pre["g1"], w1d=pre["w1d"], gmask=pre["gmask"], gx=gout, colsum_gx=pre["cs"])
                 else:
                     N.bwd1x1(gout, y2, self._wdv(c3n, f, 4 * f), y2m, g2, part(c2n), self._gview(c3n, 4 * f, f))
-                self._c2_wgrad(W, y1, g2, c2n, f, B, Ho, g2_n)
+                self._c2_wgrad(y1, g2, c2n, f, B, Ho, g2_n)
             else:
                 # conv3
-                W(N.wgrad, y2, Ho, Ho, 1, 1, 1, 0, Ho, Ho, gout, None, 0, self._gview(c3n, 4 * f, f), f, 0,
-                  reads=(gout_n,))
+                self._wgrad(y2, gout, self._gview(c3n, 4 * f, f), Ho, Ho, reads=(gout_n,))
                 self._before_write(g2_n)
-                N.igemm(gout, None, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wdv(c3n, f, 4 * f), 1, None, None, None, y2m,
-                        None, g2, 0, None, 0, 0, 0, 0, 0, part(c2n), None)
+                self._igemm(gout, self._wdv(c3n, f, 4 * f), g2, Ho, Ho, mode=IGEMM_DGRAD, mask=y2m,
+                            colsum=part(c2n))
                 # conv2 (3x3)
-                self._c2_wgrad(W, y1, g2, c2n, f, B, Ho, g2_n)
+                self._c2_wgrad(y1, g2, c2n, f, B, Ho, g2_n)
             g1 = self.g1bufs[rk][: B * Ho * Ho * f].view(B, Ho, Ho, f)
             self._before_write(f"g1_{rk}")
             if self._use_c64(f, B * Ho * Ho, Ho, self.bitmask):
                 N.conv3x3c64(g2, self._wdv(c2n, f, 9 * f), 1, g1, bits=y1m, colsum=part(c1n))
             else:
-                N.igemm(g2, None, Ho, Ho, 3, 3, 1, 1, Ho, Ho, self._wdv(c2n, f, 9 * f), 1, None, None, None, y1m,
-                        None, g1, 0, None, 0, 0, 0, 0, 0, part(c1n), None)
+                self._igemm(g2, self._wdv(c2n, f, 9 * f), g1, Ho, Ho, k=3, pad=1, mode=IGEMM_DGRAD, mask=y1m,
+                            colsum=part(c1n))
             # conv1 (+ conv0)
             nxt = (cur + 1) % len(self.gbuf)
             gx = self.gbuf[nxt][: B * H * H * cin].view(B, H, H, cin)
             gx_n = [f"gbuf{nxt}"]
             if b.proj:
                 Hx, sx = self._x_geom(bi, H, b.stride)
-                W(N.wgrad, x_in, Hx, Hx, 1, 1, sx, 0, Ho, Ho, g1, gout, f, self._gview(c1n, 5 * f, cin), cin, 0,
-                  reads=(f"g1_{rk}", gout_n))
+                self._wgrad(x_in, g1, self._gview(c1n, 5 * f, cin), Hx, Ho, stride=sx, g2=gout, co_split=f,
+                            reads=(f"g1_{rk}", gout_n))
                 W(N.wgrad_finalize, self.params, self.grads, self._fin_tabs[b.name], 4, self.scale, self.dgr,
                   self._fin_rows_n[b.name])
                 gxc, up2 = None, 1 if b.stride == 2 else 0
@@ -876,20 +891,19 @@ class HipEngine:
                     gx_n = [f"s2f{bi - 1}", "gc"]
                     up2 = 3 if Hx != H else 2   # (3: the stored block input and its mask are compact)
                 self._before_write(*gx_n)
-                N.igemm(g1, gout, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wdv(c1n, cin, 5 * f), 1, None, None, None,
-                        mask_in, None, gx, 0, gxc, 0, 0, up2, H, H, cs_in, None)
+                self._igemm(g1, self._wdv(c1n, cin, 5 * f), gx, Ho, Ho, x2=gout, mode=IGEMM_DGRAD, mask=mask_in,
+                            out2=gxc, up2=up2, Hf=H, colsum=cs_in)
                 last = L.entry(b.convs["0"].name, "kernel")
             else:
-                W(N.wgrad, x_in, H, H, 1, 1, 1, 0, Ho, Ho, g1, None, 0, self._gview(c1n, f, cin), cin, 0,
-                  reads=(f"g1_{rk}",))
+                self._wgrad(x_in, g1, self._gview(c1n, f, cin), H, Ho, reads=(f"g1_{rk}",))
                 W(N.wgrad_finalize, self.params, self.grads, self._fin_tabs[b.name], 3, self.scale, self.dgr,
                   self._fin_rows_n[b.name])
                 self._before_write(*gx_n)
                 if self._pre_fused(bi, s2):   # deferred into block bi-1's fused conv3 backward
                     pre_next = {"add": gout, "g1": g1, "w1d": self._wdv(c1n, cin, f), "gmask": mask_in, "cs": cs_in}
                 else:
-                    N.igemm(g1, None, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wdv(c1n, cin, f), 1, None, None, None,
-                            mask_in, gout, gx, 0, None, 0, 0, 0, 0, 0, cs_in, None)
+                    self._igemm(g1, self._wdv(c1n, cin, f), gx, Ho, Ho, mode=IGEMM_DGRAD, mask=mask_in, add=gout,
+                                colsum=cs_in)
                 last = L.entry(c1n, "kernel")
             done_upto(last.offset + last.size)
             cur = nxt
@@ -907,7 +921,7 @@ class HipEngine:
             gc1 = self.gbuf[gcn][: B * H1 * H1 * 64].view(B, H1, H1, 64)
             self._before_write(f"gbuf{gcn}")
             N.maxpool_bwd(gpool, self.pidx[:B], None, gc1, part(s.name))
-            W(N.wgrad, self.stem_x2[:B], Hs, Hs, 4, 4, 1, 0, H1, H1, gc1, None, 0, self.stem_dw2, STEM_K, 0)
+            self._wgrad(self.stem_x2[:B], gc1, self.stem_dw2, Hs, H1, k=4)
             W(N.stem_wgrad_fold, self.stem_dw2, self._gview(s.name, 64, 147), 64)
         W(N.wgrad_finalize, self.params, self.grads, self._fin_tabs["stem"], 1, self.scale, self.dgr,
           self._fin_rows_n["stem"])

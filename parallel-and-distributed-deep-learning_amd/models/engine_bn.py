@@ -26,7 +26,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
-from .engine import STEM_K, HipEngine
+from .engine import IGEMM_DGRAD, STEM_K, HipEngine
 from ..utils import profiling as prof
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout
 
@@ -177,13 +177,11 @@ class HipEngineBNTrain(HipEngine):
         o = self.ch[c.name]
         return arr[o:o + c.cout]
 
-    def _conv_bn(self, key, training, tabs, x, H, W, R, S, stride, pad, Ho, Wo, nn, K, out, out2=None, n_split=0):
+    def _conv_bn(self, key, training, tabs, x, out, H, Ho, nn, K, *, k=1, stride=1, pad=0, out2=None, n_split=0):
         """z = conv(x) + bias (+ batch statistics of z when training)."""
         N = self.N
-        ch = self.ch[key]
-        N.igemm_bn(x, None, H, W, R, S, stride, pad, Ho, Wo, self._wf(key, nn, K), 0, self.scale[ch:], self.shift[ch:],
-                   None, None, None, out, 0, out2, 0, n_split, 0, 0, 0, None, None,
-                   self.partial if training else None, None, None)
+        self._igemm(x, self._wf(key, nn, K), out, H, Ho, k=k, stride=stride, pad=pad, ch=self.ch[key], out2=out2,
+                    n_split=n_split, stats=self.partial if training else None)
         if training:
             cred, st, nst, maxc, _ = tabs[key]
             N.colsum_reduce(self.partial, cred, 1, self.acc)
@@ -206,9 +204,9 @@ class HipEngineBNTrain(HipEngine):
         H1, Hs = self.H1, self.Hs
         s = L.stem
         zs = self.zs[:B]
-        self._conv_bn(s.name, training, tabs, x2, Hs, Hs, 4, 4, 1, 0, H1, H1, 64, STEM_K, zs)
+        self._conv_bn(s.name, training, tabs, x2, zs, Hs, H1, 64, STEM_K, k=4)
         c1 = self.c1[:B]
-        N.bn_apply(zs, self._chs(self.bn_scale, s), self._chs(self.bn_shift, s), None, None, None, True, c1, None)
+        self._bn_relu(zs, s, c1)
         pool = self.pool[:B]
         use_bits = training and self.bitmask
         N.maxpool_fwd(c1, pool, self.pidx[:B], self.pool_bits[:B] if use_bits else None)
@@ -222,31 +220,31 @@ class HipEngineBNTrain(HipEngine):
             y1, y2, out = a["y1"][:B], a["y2"][:B], a["out"][:B]
             c1c, c2c, c3c = b.convs["1"], b.convs["2"], b.convs["3"]
             if b.proj:
-                self._conv_bn(c1c.name, training, tabs, x, H, H, 1, 1, b.stride, 0, Ho, Ho, 5 * f, cin, z["1"],
-                              z["0"], f)
+                self._conv_bn(c1c.name, training, tabs, x, z["1"], H, Ho, 5 * f, cin, stride=b.stride, out2=z["0"],
+                              n_split=f)
             else:
-                self._conv_bn(c1c.name, training, tabs, x, H, H, 1, 1, 1, 0, Ho, Ho, f, cin, z["1"])
-            N.bn_apply(z["1"], self._chs(self.bn_scale, c1c), self._chs(self.bn_shift, c1c), None, None, None, True,
-                       y1, bt.get("y1"))
-            self._conv_bn(c2c.name, training, tabs, y1, Ho, Ho, 3, 3, 1, 1, Ho, Ho, f, 9 * f, z["2"])
-            N.bn_apply(z["2"], self._chs(self.bn_scale, c2c), self._chs(self.bn_shift, c2c), None, None, None, True,
-                       y2, bt.get("y2"))
-            self._conv_bn(c3c.name, training, tabs, y2, Ho, Ho, 1, 1, 1, 0, Ho, Ho, 4 * f, f, z["3"])
-            if b.proj:
-                c0c = b.convs["0"]
-                N.bn_apply(z["3"], self._chs(self.bn_scale, c3c), self._chs(self.bn_shift, c3c), z["0"],
-                           self._chs(self.bn_scale, c0c), self._chs(self.bn_shift, c0c), True, out, bt.get("out"))
+                self._conv_bn(c1c.name, training, tabs, x, z["1"], H, Ho, f, cin)
+            self._bn_relu(z["1"], c1c, y1, bits=bt.get("y1"))
+            self._conv_bn(c2c.name, training, tabs, y1, z["2"], Ho, Ho, f, 9 * f, k=3, pad=1)
+            self._bn_relu(z["2"], c2c, y2, bits=bt.get("y2"))
+            self._conv_bn(c3c.name, training, tabs, y2, z["3"], Ho, Ho, 4 * f, f)
+            if b.proj:   # + the shortcut's BN of z0
+                self._bn_relu(z["3"], c3c, out, r=z["0"], rc=b.convs["0"], bits=bt.get("out"))
             else:
-                N.bn_apply(z["3"], self._chs(self.bn_scale, c3c), self._chs(self.bn_shift, c3c), x, None, None, True,
-                           out, bt.get("out"))
+                self._bn_relu(z["3"], c3c, out, r=x, bits=bt.get("out"))
             x = out
         pooled = self.pooled[:B]
         N.gap_fwd(x, pooled)
-        logits = self.logits[:B]
-        chd = self.ch["dense"]
-        N.igemm(pooled.view(B, 1, 1, 2048), None, 1, 1, 1, 1, 1, 0, 1, 1, self._wf("dense", self.num_classes, 2048), 2,
-                self.scale[chd:], self.shift[chd:], None, None, None, logits, 0, None, 0, 0, 0, 0, 0, None, None)
+        self._dense_fwd(pooled, B)
         return x
+
+    def _bn_relu(self, z, c, y, *, r=None, rc=None, bits=None):
+        """y = relu(bn_c(z) [+ r, or + bn_rc(r) with conv `rc`'s BN]), bits = its ReLU bitmask."""
+        a2 = b2 = None
+        if rc is not None:
+            a2, b2 = self._chs(self.bn_scale, rc), self._chs(self.bn_shift, rc)
+        self.N.bn_apply(z, self._chs(self.bn_scale, c), self._chs(self.bn_shift, c), r=r, a2=a2, b2=b2, relu=True,
+                        y=y, bits=bits)
 
     # ------------------------------------------------------------------ backward
     def _bn_layer(self, c, M):
@@ -258,24 +256,23 @@ class HipEngineBNTrain(HipEngine):
         """dz (and dz2 of the shortcut BN fed by the same g) from g = dL/d(BN output)."""
         N = self.N
         if z2 is None:
-            N.bn_bwd_reduce(g, z, None, self._chs(self.bn_mean, c), None, self._chs(self.bsg, c),
-                            self._chs(self.bsgx, c), None, None)
-            N.bn_bwd_apply(g, z, None, self._bn_layer(c, M), [], self.params, self.bn_mean, self.bn_inv, self.bsg,
-                           self.bsgx, out, None, self.grads, self.bcoef)
+            N.bn_bwd_reduce(g, z, mean=self._chs(self.bn_mean, c), sg=self._chs(self.bsg, c),
+                            sgx=self._chs(self.bsgx, c))
+            self._bn_bwd_apply(g, z, c, M, out)
         else:
             N.bn_bwd_reduce(g, z, z2, self._chs(self.bn_mean, c), self._chs(self.bn_mean, c2), self._chs(self.bsg, c),
                             self._chs(self.bsgx, c), self._chs(self.bsg, c2), self._chs(self.bsgx, c2))
             N.bn_bwd_apply(g, z, z2, self._bn_layer(c, M), self._bn_layer(c2, M), self.params, self.bn_mean,
                            self.bn_inv, self.bsg, self.bsgx, out, out2, self.grads, self.bcoef)
 
-    def _dgrad_bn_bwd(self, g_in, Ho, R, pad, w, mask, g, z, c, M):
+    def _dgrad_bn_bwd(self, g_in, Ho, k, pad, w, mask, g, z, c, M):
         """g = dgrad(g_in) * mask with the BN-backward sums (sum g, sum g*(z - mean)) of conv `c`'s
         BN fused into the dgrad epilogue (stats rows folded into bsg / bsgx: no bn_bwd_reduce
         pass over g and z), then dz = bn_bwd_apply(g, z) in place."""
         N = self.N
         f = c.cout
-        N.igemm_bn(g_in, None, Ho, Ho, R, R, 1, pad, Ho, Ho, w, 1, None, None, None, mask, None, g, 0, None, 0, 0,
-                   0, 0, 0, None, None, self.partial, z, self._chs(self.bn_mean, c))
+        self._igemm(g_in, w, g, Ho, Ho, k=k, pad=pad, mode=IGEMM_DGRAD, mask=mask, stats=self.partial, bn_z=z,
+                    bn_mean=self._chs(self.bn_mean, c))
         key = (c.name, M)
         tab = self._bwd_tabs.get(key)
         if tab is None:
@@ -289,8 +286,8 @@ class HipEngineBNTrain(HipEngine):
 
     def _bn_bwd_apply(self, g, z, c, M, out):
         """dz from g once bsg / bsgx of conv `c`'s BN hold (sum g, sum g*(z - mean))."""
-        self.N.bn_bwd_apply(g, z, None, self._bn_layer(c, M), [], self.params, self.bn_mean, self.bn_inv, self.bsg,
-                            self.bsgx, out, None, self.grads, self.bcoef)
+        self.N.bn_bwd_apply(g, z, l=self._bn_layer(c, M), params=self.params, mean=self.bn_mean, inv=self.bn_inv,
+                            sg=self.bsg, sgx=self.bsgx, dz=out, grads=self.grads, coef=self.bcoef)
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
                          bucket_cb: Optional[Callable[[int], None]] = None, buckets=None):
@@ -321,15 +318,7 @@ class HipEngineBNTrain(HipEngine):
                 nb[0] += 1
 
         # ---- head (as the frozen engine)
-        pooled = self.pooled[:B]
-        chd = self.ch["dense"]
-        N.wgrad(pooled.view(B, 1, 1, 2048), 1, 1, 1, 1, 1, 0, 1, 1, dl, None, 0,
-                self._gview("dense", self.num_classes, 2048), 2048, 0)
-        N.colsum(dl, self.num_classes, self.colsum[chd:])
-        dpooled = self.dpooled[:B]
-        N.igemm(dl.view(B, 1, 1, self.ncls_pad), None, 1, 1, 1, 1, 1, 0, 1, 1,
-                self._wdv("dense", 2048, self.ncls_pad), 1, None, None, None, None, None, dpooled, 0,
-                None, 0, 0, 0, 0, 0, None, None)
+        dpooled = self._dense_bwd(self.pooled[:B], dl, B, side=False)   # (all on the compute stream)
         N.bn_grad(self.params, self.grads, self._bng_dense, 1, self.colsum, self.dgr, self.scale, BN_EPS)
         e = L.entry("dense", "kernel")
         done_upto(e.offset + e.size)
@@ -369,14 +358,12 @@ class HipEngineBNTrain(HipEngine):
             else:
                 self._bn_bwd(gout, z["3"], c3c, M, dz3)
             # conv3
-            W(N.wgrad, y2, Ho, Ho, 1, 1, 1, 0, Ho, Ho, dz3, None, 0, self._gview(c3c.name, 4 * f, f), f, 0,
-              reads=(("z3", j),))
+            self._wgrad(y2, dz3, self._gview(c3c.name, 4 * f, f), Ho, Ho, reads=(("z3", j),))
             g2 = self.g2bufs[j][: M * f].view(B, Ho, Ho, f)
             self._before_write(("g2", j))
             self._dgrad_bn_bwd(dz3, Ho, 1, 0, self._wdv(c3c.name, f, 4 * f), y2m, g2, z["2"], c2c, M)
             # conv2 (3x3)
-            W(N.wgrad, y1, Ho, Ho, 3, 3, 1, 1, Ho, Ho, g2, None, 0, self._gview(c2c.name, f, 9 * f), 9 * f, 0,
-              reads=(("g2", j),))
+            self._wgrad(y1, g2, self._gview(c2c.name, f, 9 * f), Ho, Ho, k=3, pad=1, reads=(("g2", j),))
             g1 = self.g1bufs[j][: M * f].view(B, Ho, Ho, f)
             self._before_write(("g1", j))
             self._dgrad_bn_bwd(g2, Ho, 3, 1, self._wdv(c2c.name, f, 9 * f), y1m, g1, z["1"], c1c, M)
@@ -385,22 +372,20 @@ class HipEngineBNTrain(HipEngine):
             gx = self.gbuf[nxt][: B * H * H * cin].view(B, H, H, cin)
             gx_key = ("g", nxt)
             if b.proj:
-                W(N.wgrad, x_in, H, H, 1, 1, b.stride, 0, Ho, Ho, g1, gout, f, self._gview(c1c.name, 5 * f, cin), cin, 0,
-                  reads=(("g1", j), gkey))
+                self._wgrad(x_in, g1, self._gview(c1c.name, 5 * f, cin), H, Ho, stride=b.stride, g2=gout, co_split=f,
+                            reads=(("g1", j), gkey))
                 up2 = 1 if b.stride == 2 else 0
                 if bi - 1 in s2:   # grid positions only, into the pre-zeroed full-resolution buffer
                     gx, up2 = self.s2full[bi - 1][: B * H * H * cin].view(B, H, H, cin), 2
                     gx_key = ("s2", bi - 1)
                 self._before_write(gx_key)
-                N.igemm(g1, gout, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wdv(c1c.name, cin, 5 * f), 1, None, None, None,
-                        mask_in, None, gx, 0, None, 0, 0, up2, H, H, None, None)
+                self._igemm(g1, self._wdv(c1c.name, cin, 5 * f), gx, Ho, Ho, x2=gout, mode=IGEMM_DGRAD, mask=mask_in,
+                            up2=up2, Hf=H)
                 last = L.entry(b.convs["0"].name, "kernel")
             else:
-                W(N.wgrad, x_in, H, H, 1, 1, 1, 0, Ho, Ho, g1, None, 0, self._gview(c1c.name, f, cin), cin, 0,
-                  reads=(("g1", j),))
+                self._wgrad(x_in, g1, self._gview(c1c.name, f, cin), H, Ho, reads=(("g1", j),))
                 self._before_write(gx_key)
-                N.igemm(g1, None, Ho, Ho, 1, 1, 1, 0, Ho, Ho, self._wdv(c1c.name, cin, f), 1, None, None, None,
-                        mask_in, gout, gx, 0, None, 0, 0, 0, 0, 0, None, None)
+                self._igemm(g1, self._wdv(c1c.name, cin, f), gx, Ho, Ho, mode=IGEMM_DGRAD, mask=mask_in, add=gout)
                 last = L.entry(c1c.name, "kernel")
             done_upto(last.offset + last.size)
             cur = nxt
@@ -413,8 +398,7 @@ class HipEngineBNTrain(HipEngine):
         self._before_write(("g", gi))
         N.maxpool_bwd(gpool, self.pidx[:B], None, gc1, None)
         self._bn_bwd(gc1, self.zs[:B], s, B * H1 * H1, gc1)
-        W(N.wgrad, self.stem_x2[:B], Hs, Hs, 4, 4, 1, 0, H1, H1, gc1, None, 0, self.stem_dw2, STEM_K, 0,
-          reads=(("g", gi),))
+        self._wgrad(self.stem_x2[:B], gc1, self.stem_dw2, Hs, H1, k=4, reads=(("g", gi),))
         W(N.stem_wgrad_fold, self.stem_dw2, self._gview(s.name, 64, 147), 64)
         self._join_side()
         done_upto(L.kernels_end)

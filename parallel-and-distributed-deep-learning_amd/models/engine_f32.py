@@ -296,8 +296,8 @@ class HipF32Engine:
 
     def _conv(self, x, R, stride, pad, Ho, w, out, scale=None, shift=None, res=None, relu=0, epi=EPI_FWD,
               add=None, mask=None, up2=0, colsum=None):
-        self.N.conv_f32_epi(x, R, R, stride, pad, Ho, Ho, w, epi, scale, shift, res, relu, add, mask, up2, out,
-                            colsum)
+        self.N.conv_f32_epi(x, R, R, stride, pad, Ho, Ho, w, epi, scale=scale, shift=shift, res=res, relu=relu, add=add,
+                            mask=mask, up2=up2, y=out, colsum=colsum)
 
     def _fwd_conv(self, c, x, out, res=None, relu=1):
         ch = self.ch[c.name]
@@ -584,8 +584,8 @@ class HipF32EngineBNTrain(HipF32Engine):
         self._conv(x, R, stride, pad, Ho, w, z, self.scale[ch:], self.shift[ch:], None, 0)
         if training:
             M = z.numel() // c.cout
-            self.N.bn_bwd_reduce(z, z, None, self.zero_c[:c.cout], None, self.acc[ch:ch + c.cout],
-                                 self.acc[self.nch + ch:self.nch + ch + c.cout], None, None)
+            self.N.bn_bwd_reduce(z, z, mean=self.zero_c[:c.cout], sg=self.acc[ch:ch + c.cout],
+                                 sgx=self.acc[self.nch + ch:self.nch + ch + c.cout])
             self.N.bn_stats(self.acc, self._stats(c, M), 1, c.cout, True, self.params, self.bn_mean, self.bn_inv,
                             self.bn_scale, self.bn_shift, BN_EPS, BN_MOMENTUM)
 
@@ -601,7 +601,7 @@ class HipF32EngineBNTrain(HipF32Engine):
         s = L.stem
         zs, c1 = self.zs[:B], self.c1[:B]
         self._z(s, x2, 4, 1, 0, self.H1, self.wf32[:64 * STEM_K].view(64, STEM_K), zs, training)
-        N.bn_apply(zs, self._chs(self.bn_scale, s), self._chs(self.bn_shift, s), None, None, None, True, c1, None)
+        N.bn_apply(zs, self._chs(self.bn_scale, s), self._chs(self.bn_shift, s), relu=True, y=c1)
         pool = self.pool[:B]
         N.maxpool_fwd_f32(c1, pool, self.pidx[:B])
         x = pool
@@ -614,18 +614,18 @@ class HipF32EngineBNTrain(HipF32Engine):
             self._z(c["1"], x, 1, b.stride, 0, Ho, self._w(c["1"].name, f, b.cin), z["1"], training)
             if b.proj:
                 self._z(c["0"], x, 1, b.stride, 0, Ho, self._w(c["0"].name, 4 * f, b.cin), z["0"], training)
-            N.bn_apply(z["1"], self._chs(self.bn_scale, c["1"]), self._chs(self.bn_shift, c["1"]), None, None, None,
-                       True, a["y1"], None)
+            N.bn_apply(z["1"], self._chs(self.bn_scale, c["1"]), self._chs(self.bn_shift, c["1"]), relu=True,
+                       y=a["y1"])
             self._z(c["2"], a["y1"], 3, 1, 1, Ho, self._w(c["2"].name, f, 9 * f), z["2"], training)
-            N.bn_apply(z["2"], self._chs(self.bn_scale, c["2"]), self._chs(self.bn_shift, c["2"]), None, None, None,
-                       True, a["y2"], None)
+            N.bn_apply(z["2"], self._chs(self.bn_scale, c["2"]), self._chs(self.bn_shift, c["2"]), relu=True,
+                       y=a["y2"])
             self._z(c["3"], a["y2"], 1, 1, 0, Ho, self._w(c["3"].name, 4 * f, f), z["3"], training)
             if b.proj:
                 N.bn_apply(z["3"], self._chs(self.bn_scale, c["3"]), self._chs(self.bn_shift, c["3"]), z["0"],
-                           self._chs(self.bn_scale, c["0"]), self._chs(self.bn_shift, c["0"]), True, a["out"], None)
+                           self._chs(self.bn_scale, c["0"]), self._chs(self.bn_shift, c["0"]), relu=True, y=a["out"])
             else:
-                N.bn_apply(z["3"], self._chs(self.bn_scale, c["3"]), self._chs(self.bn_shift, c["3"]), x, None, None,
-                           True, a["out"], None)
+                N.bn_apply(z["3"], self._chs(self.bn_scale, c["3"]), self._chs(self.bn_shift, c["3"]), r=x, relu=True,
+                           y=a["out"])
             x = a["out"]
         pooled = self.pooled[:B]
         N.gap_fwd_f32(x, pooled)
@@ -645,10 +645,10 @@ class HipF32EngineBNTrain(HipF32Engine):
         fed by the same gradient (a projection block's shortcut)."""
         N = self.N
         if z2 is None:
-            N.bn_bwd_reduce(g, z, None, self._chs(self.bn_mean, c), None, self._chs(self.bsg, c),
-                            self._chs(self.bsgx, c), None, None)
-            N.bn_bwd_apply(g, z, None, self._bn_layer(c, M), [], self.params, self.bn_mean, self.bn_inv, self.bsg,
-                           self.bsgx, out, None, self.grads, self.bcoef)
+            N.bn_bwd_reduce(g, z, mean=self._chs(self.bn_mean, c), sg=self._chs(self.bsg, c),
+                            sgx=self._chs(self.bsgx, c))
+            N.bn_bwd_apply(g, z, l=self._bn_layer(c, M), params=self.params, mean=self.bn_mean, inv=self.bn_inv,
+                           sg=self.bsg, sgx=self.bsgx, dz=out, grads=self.grads, coef=self.bcoef)
         else:
             N.bn_bwd_reduce(g, z, z2, self._chs(self.bn_mean, c), self._chs(self.bn_mean, c2), self._chs(self.bsg, c),
                             self._chs(self.bsgx, c), self._chs(self.bsg, c2), self._chs(self.bsgx, c2))

@@ -41,8 +41,8 @@ def test_igemm_stats_epilogue(case):
     out = torch.empty(n, ho, ho, co, dtype=torch.bfloat16, device=dev)
     rows = nat.igemm_partial_rows(M, co, K)
     part = torch.full((rows * 2 * co,), float("nan"), device=dev)
-    nat.igemm_bn(x, None, h, h, r, r, st, pad, ho, ho, w.view(co, -1), 0, ones, bias, None, None, None, out, 0, None,
-                 0, 0, 0, 0, 0, None, None, part, None, None)
+    nat.igemm(x, None, h, h, r, r, st, pad, ho, ho, w.view(co, -1), 0, ones, bias, None, None, None, out, 0, None,
+              0, 0, 0, 0, 0, None, None, part, None, None)
     acc = torch.zeros(2 * co, device=dev)
     tab = torch.frombuffer(bytearray(struct.pack("<q4i", 0, rows, 2 * co, 0, 0)), dtype=torch.uint8).to(dev)
     nat.colsum_reduce(part, tab, 1, acc)
@@ -69,8 +69,8 @@ def test_dgrad_fused_bn_backward_sums(case):
     M, K = n * h * h, r * r * co
     rows = nat.igemm_partial_rows(M, cin, K, True)
     part = torch.full((rows * 2 * cin,), float("nan"), device=dev)
-    nat.igemm_bn(g_in, None, h, h, r, r, 1, r - 1 - pad, h, h, wt.view(cin, -1), 1, None, None, None, mask, None, out,
-                 0, None, 0, 0, 0, 0, 0, None, None, part, z, mean)
+    nat.igemm(g_in, None, h, h, r, r, 1, r - 1 - pad, h, h, wt.view(cin, -1), 1, None, None, None, mask, None, out,
+              0, None, 0, 0, 0, 0, 0, None, None, part, z, mean)
     ref = torch.nn.grad.conv2d_input((n, cin, h, h), w.float().permute(0, 3, 1, 2), g_in.float().permute(0, 3, 1, 2),
                                      padding=pad).permute(0, 2, 3, 1) * (mask.float() > 0)
     assert rel(out, ref) < 1e-2
