@@ -674,6 +674,15 @@ void softmax_xent(Tensor logits, Tensor labels, int64_t ncls, double gscale, Ten
                                f32p(correct), cur_stream()),
      "softmax_xent");
 }
+void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out) {
+  PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda() && labels.is_contiguous(), "labels int64 GPU");
+  PCHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && ncls <= logits.size(1),
+         "eval_metrics: logits [B][>= ncls], labels [B]");
+  PCHECK(out.numel() == 3 && out.is_contiguous(), "eval_metrics: out is 3 contiguous floats");
+  ok(pddl::eval_metrics_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0), (int)ncls,
+                               (int)k, f32p(out), cur_stream()),
+     "eval_metrics");
+}
 void prep(Tensor params, Tensor table, int64_t nlayers, int64_t max_elems, Tensor wbf, Tensor scale, Tensor shift,
           double eps, int64_t parts) {
   PCHECK(table.is_cuda() && table.scalar_type() == torch::kUInt8, "prep table");
@@ -876,6 +885,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gap_bwd", &gap_bwd, REL);
   m.def("colsum", &colsum, REL);
   m.def("softmax_xent", &softmax_xent, REL);
+  m.def("eval_metrics", &eval_metrics, REL);
   m.def("colsum_reduce", &colsum_reduce, REL);
   m.def("allow_knob_changes", [](bool on) { g_knob_tuning.store(on); }, py::arg("on") = true);
   m.def("knobs_frozen", []() { return g_launched.load() && !g_knob_tuning.load(); });

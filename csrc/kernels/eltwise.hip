@@ -772,6 +772,47 @@ const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* lab
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 
+// ---------------------------------------------------------------------- eval-metrics
+// The evaluation head: one wave per example, no dlogits.  out[0] += logsumexp - logit[label];
+// rank = #{j < ncls : logit[j] > logit[label] or (logit[j] == logit[label] and j < label)}
+// (equal logits ordered by index, so rank == 0 is softmax_xent's "first argmax == label");
+// out[1] += (rank == 0); out[2] += (rank < k).  Columns >= ncls of a row are never read.
+__global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
+                                    int B, int ncls, int k, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* row = logits + (long)b * ldl;
+  const int lab = (int)labels[b];
+  const float vl = row[lab];
+  float mx = -INFINITY; int rank = 0;
+  for (int j = lane; j < ncls; j += 64) {
+    const float v = row[j];
+    mx = fmaxf(mx, v);
+    rank += (v > vl || (v == vl && j < lab)) ? 1 : 0;
+  }
+  mx = warp_max(mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+  float se = 0.f;
+  for (int j = lane; j < ncls; j += 64) se += __expf(row[j] - mx);
+  se = warp_sum(se);
+  if (lane == 0) {
+    unsafeAtomicAdd(out + 0, mx + __logf(se) - vl);
+    unsafeAtomicAdd(out + 1, rank == 0 ? 1.f : 0.f);
+    unsafeAtomicAdd(out + 2, rank < k ? 1.f : 0.f);
+  }
+}
+const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k, float* out,
+                                hipStream_t s) {
+  if (k < 1) return "eval_metrics: k < 1";
+  if (ldl < ncls) return "eval_metrics: ldl < ncls";
+  if (B <= 0) return nullptr;
+  hipLaunchKernelGGL(eval_metrics_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, k, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+
 // ----------------------------------------------------------------------------- prep
 // After each optimizer step: fp32 master -> bf16 forward weights [cout][kpad] (zero padded),
 // bf16 dgrad weights W'[c][R-1-r][S-1-s][co] = a[co] * W[co][r][s][c], and the folded

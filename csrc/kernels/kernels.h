@@ -249,6 +249,9 @@ int maxpool_bwd_partial_rows(int B, int H, int W, int C);
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
                                 float gscale, uint16_t* dlogits, int ldd, float* loss_sum, float* correct,
                                 hipStream_t s);
+// Evaluation head (no dlogits): out[0] += loss sum, out[1] += top-1 hits, out[2] += top-k hits.
+const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k,
+                                float* out, hipStream_t s);
 
 // Per-layer parameter preparation after every optimizer step (one launch for all layers).
 struct PrepLayer {

@@ -45,6 +45,10 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
             sys.stderr.write("--resume is not supported for --strategy ps: the parameter-server job restarts from "
                              "--weights (the final PS checkpoint holds the trained variables, no optimizer state)\n")
             return 2
+        if cfg.evaluate:
+            sys.stderr.write("--evaluate is not supported for --strategy ps: score the PS checkpoint with the single "
+                             "or mirrored script (--evaluate --weights <the final PS checkpoint>)\n")
+            return 2
         from .parallel.parameter_server import run_ps_job
         return run_ps_job(cfg)
     if cfg.roctx:
@@ -60,6 +64,8 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
         # the reference's informational print (imagenet-resnet50-multiworkers.py:76; 10M-image
         # epoch assumption, Q9) -- printed by every worker, as there
         print("Steps per epoch: ", int((10000000 / strategy.num_replicas_in_sync) / strategy.world), flush=True)
+    if cfg.evaluate:
+        return _evaluate(cfg, strategy, trainer)
     cbs = default_callbacks(cfg, strategy)
     initial_epoch = 0
     rs = getattr(strategy, "resume_state", None)
@@ -79,6 +85,11 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
         trainer.save(fname)
     if cfg.strategy in ("horovod", "multiworker"):
         print("All done for rank", strategy.rank, flush=True)
+    _leave_process_group()
+    return 0
+
+
+def _leave_process_group():
     try:
         import torch.distributed as dist
         if dist.is_initialized():
@@ -86,4 +97,25 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
             dist.destroy_process_group()
     except Exception:
         pass
+
+
+def _evaluate(cfg, strategy, trainer) -> int:
+    """--evaluate: Keras `model.evaluate` of the loaded weights over the validation split (bounded
+    by --validation-steps / --max-steps).  Nothing is trained and nothing is saved."""
+    import json
+    import time
+    strategy.sync()
+    t0 = time.time()
+    m = trainer.evaluate(top5=True)
+    strategy.sync()
+    dt = max(time.time() - t0, 1e-9)
+    if strategy.is_chief:
+        print(f"evaluate - loss: {m['loss']:.4f} - accuracy: {m['accuracy']:.4f} - top5_accuracy: "
+              f"{m['top5_accuracy']:.4f} - {m['images']} images - {m['images'] / dt:.1f} img/s", flush=True)
+        if cfg.metrics_jsonl:
+            rec = {"evaluate": True, **m, "images_per_sec": m["images"] / dt,
+                   "replicas": strategy.num_replicas_in_sync}
+            with open(cfg.metrics_jsonl, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+    _leave_process_group()
     return 0

@@ -80,6 +80,7 @@ class TrainConfig:
     graphs: Optional[bool] = None                  # HIP graphs: None = auto (on for Mirrored / local replicas)
     roctx: bool = False                            # roctx ranges per step phase (utils/profiling.py)
     max_steps: Optional[int] = None                # cap steps per epoch (smoke / bench)
+    evaluate: bool = False                         # --evaluate: score the validation split and exit (no training)
 
     def replace(self, **kw) -> "TrainConfig":
         return dataclasses.replace(self, **kw)
@@ -146,6 +147,8 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--steps-per-epoch", type=int, dest="steps_per_epoch")
     a("--validation-steps", type=int, dest="validation_steps")
     a("--max-steps", type=int, dest="max_steps")
+    a("--evaluate", action="store_true", default=None,
+      help="score the validation split (loss, top-1, top-5) with --weights / --resume loaded; trains and saves nothing")
     a("--bucket-mb", type=float, dest="bucket_mb")
     a("--grad-dtype", choices=["fp32", "bf16"], dest="grad_dtype")
     a("--weights", type=str)

@@ -168,6 +168,8 @@ class HipEngine:
         self.stem_dw2 = self.ws[o:o + nst].view(64, STEM_K)   # s2d-domain stem weight grad
         self.scale = torch.ones(self.nch, dtype=torch.float32, device=dev)
         self.shift = torch.zeros(self.nch, dtype=torch.float32, device=dev)
+        # evaluate_topk's [loss sum, top-1 hits, top-k hits]: its own buffer, outside the per-step workspace
+        self.eval_stats = torch.zeros(3, dtype=torch.float32, device=dev)
         self._build_weight_tables()
         self._alloc_acts(batch)
         # split-K workspace of the small-M layers (igemm.hip: stage 5 at small batches, the Dense
@@ -952,6 +954,17 @@ class HipEngine:
         N.softmax_xent(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
                        self.stats[1:2])
         return self.stats
+
+    @torch.no_grad()
+    def evaluate_topk(self, images, labels, k=5):
+        """[loss sum, top-1 hits, top-k hits] of the batch (eval_metrics: the head without dlogits)."""
+        B = images.shape[0]
+        assert B <= self.cap
+        self.eval_stats.zero_()
+        lab = self._labels(labels, B)
+        self._forward(images, B, False, None, (0, 0))
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats)
+        return self.eval_stats
 
 
 def make_hip_engine(layout: ParamLayout, batch: int, bn_mode: str = "frozen", **kw) -> HipEngine:

@@ -79,6 +79,8 @@ class HipF32Engine:
         self.stem_dw2 = self.ws[o:o + nst].view(64, STEM_K)
         self.scale = torch.ones(self.nch, **f32)
         self.shift = torch.zeros(self.nch, **f32)
+        # evaluate_topk's [loss sum, top-1 hits, top-k hits]: its own buffer, outside the per-step workspace
+        self.eval_stats = torch.zeros(3, **f32)
         self._tables()
         self._alloc(batch)
 
@@ -479,6 +481,17 @@ class HipF32Engine:
         self.N.softmax_xent_f32(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
                                 self.stats[1:2])
         return self.stats
+
+    @torch.no_grad()
+    def evaluate_topk(self, images, labels, k=5):
+        """[loss sum, top-1 hits, top-k hits] of the batch (eval_metrics: the head without dlogits)."""
+        B = images.shape[0]
+        assert B <= self.cap
+        self.eval_stats.zero_()
+        lab = self._labels(labels, B)
+        self._forward(images, B, False, None, (0, 0))
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats)
+        return self.eval_stats
 
 
 _STAT_FMT = "<8if i"   # BnStatLayer (csrc/kernels/kernels.h)

@@ -244,3 +244,18 @@ class TorchEngine:
         lab = labels.to(self.device)
         loss_sum = F.cross_entropy(logits, lab, reduction="sum")
         return torch.stack([loss_sum, (logits.argmax(1) == lab).sum().float()])
+
+    @torch.no_grad()
+    def evaluate_topk(self, images, labels, k=5):
+        """[loss sum, top-1 hits, top-k hits].  rank = #{j : logit[j] > logit[label] or (logit[j] ==
+        logit[label] and j < label)}: equal logits are ordered by index, so rank == 0 is
+        evaluate's "first argmax == label"; a top-k hit is rank < k."""
+        x = preprocess(images.to(self.device), self.crop, False)
+        self.model.stats = self.params
+        logits = self.model.logits(self.params, x, training=False)
+        lab = labels.to(self.device)
+        loss_sum = F.cross_entropy(logits, lab, reduction="sum")
+        vl = logits.gather(1, lab[:, None])
+        idx = torch.arange(logits.shape[1], device=logits.device)[None, :]
+        rank = ((logits > vl) | ((logits == vl) & (idx < lab[:, None]))).sum(1)
+        return torch.stack([loss_sum, (rank == 0).sum().float(), (rank < k).sum().float()])

@@ -224,7 +224,10 @@ class Strategy:
         for _, opt in self._replicas():
             opt.lr = lr
 
-    def eval_step(self, images, labels):
+    def eval_step(self, images, labels, top5: bool = False):
+        """[loss sum, top-1 hits] of the batch, or with top5 [loss sum, top-1 hits, top-5 hits]."""
+        if top5:
+            return self.engine.evaluate_topk(images, labels).clone()
         return self.engine.evaluate(images, labels).clone()
 
     def reduce_metrics(self, t: torch.Tensor) -> torch.Tensor:
@@ -527,6 +530,11 @@ class MultiWorkerStrategy(HorovodStrategy):
         self._fault_tick()
         return self.mirror.step(images, labels, self.global_batch)
 
+    def eval_step(self, images, labels, top5: bool = False):
+        if not hasattr(self, "mirror"):
+            return super().eval_step(images, labels, top5)
+        return self.mirror.evaluate(images, labels, top5)   # (ordering against graphed steps: MirroredStrategy.eval_step)
+
     def broadcast_state(self, trainer, root=0):
         if hasattr(self, "mirror"):
             self.mirror.broadcast()
@@ -641,6 +649,64 @@ class _LocalReplicas:
         for s in stats[1:]:
             out = out + s.to(self.devices[0])
         return out
+
+    # ------------------------------------------------------------------ evaluation
+    def _shares(self, B: int):
+        """[start, end) of every replica's share of a B-image batch: shares differ by at most one
+        image and no image is dropped (a ragged last validation batch is scored whole)."""
+        q, r = divmod(B, self.R)
+        edges = [0]
+        for i in range(self.R):
+            edges.append(edges[-1] + q + (1 if i < r else 0))
+        return list(zip(edges, edges[1:]))
+
+    def evaluate(self, images, labels, top5: bool = False):
+        """Inference metrics of one batch over the local replicas: [loss sum, top-1 hits] or with
+        top5 [loss sum, top-1 hits, top-5 hits], summed on device 0.  Every replica scores its
+        share on its own engine (in chunks of at most the engine's capacity) on its device's
+        current stream; a replica whose share is empty is skipped.  No collective: the
+        cross-process sum is reduce_metrics'."""
+        stats = [None] * self.R
+        errors = [None] * self.R
+        # every replica's chunks, placed on its device by this thread (as _split does for a step)
+        chunks = []
+        for (eng, _), d, (s, e) in zip(self.replicas, self.devices, self._shares(images.shape[0])):
+            cap = getattr(eng, "cap", eng.batch)
+            chunks.append([(images[c:min(c + cap, e)].to(d, non_blocking=True),
+                            labels[c:min(c + cap, e)].to(d, non_blocking=True)) for c in range(s, e, cap)])
+        # (a thread starts on the default stream: hand each replica thread this thread's current one)
+        amb = [torch.cuda.current_stream(d) if d.type == "cuda" else None for d in self.devices]
+
+        def score(i):
+            eng, _ = self.replicas[i]
+            for im, lb in chunks[i]:
+                part = (eng.evaluate_topk(im, lb) if top5 else eng.evaluate(im, lb)).clone()
+                stats[i] = part if stats[i] is None else stats[i] + part
+
+        def run(i):
+            try:
+                if amb[i] is None:
+                    return score(i)
+                torch.cuda.set_device(self.devices[i])
+                with torch.cuda.stream(amb[i]):
+                    score(i)
+            except BaseException as e:   # (re-raised by the calling thread: a replica thread must not fail silently)
+                errors[i] = e
+
+        busy = [i for i in range(self.R) if chunks[i]]
+        if self.gpu and self.R > 1:
+            th = [threading.Thread(target=run, args=(i,)) for i in busy]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+        else:
+            for i in busy:
+                run(i)
+        for e in errors:
+            if e is not None:
+                raise e
+        return self._sum_stats([s for s in stats if s is not None])
 
     # ------------------------------------------------------------------ graphed step
     def _bucket_mb(self) -> float:
@@ -1008,6 +1074,14 @@ class MirroredStrategy(Strategy):
 
     def compute_gradients(self, images, labels):
         return self.mirror.compute_gradients(images, labels, self.global_batch)
+
+    def eval_step(self, images, labels, top5: bool = False):
+        # Every replica scores its share of the batch on its device's ambient (current) stream.
+        # Graphed replicas replay on replay_stream, but the optimizer group launch hands the step
+        # back to the ambient streams (P["out_ev"] -> P["amb"]) and the next step's first launch
+        # waits on them again, so an evaluation enqueued here runs after the last update and
+        # before the next replay.
+        return self.mirror.evaluate(images, labels, top5)
 
     def broadcast_state(self, trainer, root=0):
         self.mirror.broadcast()

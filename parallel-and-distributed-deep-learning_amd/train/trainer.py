@@ -10,6 +10,7 @@ strategy (chief-only write, fixing the reference's every-worker-same-file race, 
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import sys
 import time
@@ -68,6 +69,47 @@ class Trainer:
     def save(self, path: str, include_optimizer: bool = True, epoch: Optional[int] = None):
         prog = self.progress(epoch) if epoch is not None else None
         self.strategy.save(self, path, include_optimizer=include_optimizer, progress=prog)
+
+    # -- evaluation
+    def _score(self, pipe, steps: int, top5: bool) -> torch.Tensor:
+        """[loss sum, top-1 hits, top-5 hits (0 unless top5), images] over up to `steps` batches of
+        `pipe`, summed in float64 on the metrics device and reduced ONCE across the job's
+        replicas (nothing is reduced per step, so ranks may see different batch counts)."""
+        st = self.strategy
+        acc = torch.zeros(4, dtype=torch.float64, device=st.metrics_device)
+        it = pipe.iterate(st.device, epoch=0)
+        for _ in range(steps):
+            try:
+                vi, vl = next(it)
+            except StopIteration:
+                break
+            if top5:
+                acc[:3] += st.eval_step(vi, vl, top5=True).to(acc.device, torch.float64)
+            else:
+                acc[:2] += st.eval_step(vi, vl).to(acc.device, torch.float64)
+            acc[3] += vi.shape[0]
+        return st.reduce_metrics(acc)
+
+    def evaluate(self, steps: Optional[int] = None, top5: bool = True) -> Dict[str, float]:
+        """Keras `model.evaluate` over the strategy's validation pipeline: loss, accuracy,
+        top5_accuracy (when asked) and the number of images scored.  The last, ragged batch is
+        kept (drop_remainder=False), so a real validation split is scored whole."""
+        cfg = self.cfg
+        pipe = dataclasses.replace(self.strategy.val_pipeline(), drop_remainder=False)
+        n = steps or cfg.validation_steps
+        if not pipe.repeat:
+            n = min(n or pipe.num_batches(), pipe.num_batches())
+        if cfg.max_steps:
+            n = min(n or cfg.max_steps, cfg.max_steps)
+        if not n:
+            raise ValueError("evaluate over a repeating pipeline needs steps, --validation-steps or --max-steps")
+        t = self._score(pipe, n, top5)
+        den = max(float(t[3]), 1.0)
+        out = {"loss": float(t[0]) / den, "accuracy": float(t[1]) / den}
+        if top5:
+            out["top5_accuracy"] = float(t[2]) / den
+        out["images"] = int(t[3])
+        return out
 
     # -- the loop
     def fit(self, epochs: int, callbacks: Optional[List[Callback]] = None, validation: bool = True,
@@ -133,19 +175,9 @@ class Trainer:
                                                                  device=acc.device)]))
             logs = {"loss": tot[0] / max(tot[2], 1), "accuracy": tot[1] / max(tot[2], 1)}
             if val_pipe is not None and vsteps:
-                vacc = torch.zeros(3, dtype=torch.float64, device=st.metrics_device)
-                vit = val_pipe.iterate(st.device, epoch=0)
-                for vs in range(vsteps):
-                    try:
-                        vi, vl = next(vit)
-                    except StopIteration:
-                        break
-                    s = st.eval_step(vi, vl)
-                    vacc[:2] += s.to(vacc.device, torch.float64)
-                    vacc[2] += vi.shape[0]
-                vt = st.reduce_metrics(vacc)
-                logs["val_loss"] = vt[0] / max(vt[2], 1)
-                logs["val_accuracy"] = vt[1] / max(vt[2], 1)
+                vt = self._score(val_pipe, vsteps, top5=False)
+                logs["val_loss"] = vt[0] / max(vt[3], 1)
+                logs["val_accuracy"] = vt[1] / max(vt[3], 1)
             logs = {k: float(v) for k, v in logs.items()}
             dt = time.time() - t0
             for cb in cbs:
