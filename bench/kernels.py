@@ -19,6 +19,7 @@ FWD = [  # name, H, C, Cout, R, stride, pad
     ("s4.c2 3x3 256", 14, 256, 256, 3, 1, 1), ("s5.c2 3x3 512", 7, 512, 512, 3, 1, 1),
     ("s4.c1 1x1 1024>256", 14, 1024, 256, 1, 1, 0), ("s5.c1 1x1 2048>512", 7, 2048, 512, 1, 1, 0),
     ("s3.c1 1x1 512>128", 28, 512, 128, 1, 1, 0), ("s4.c3 1x1 256>1024", 14, 256, 1024, 1, 1, 0),
+    ("s3.c2 3x3 128 s2", 56, 128, 128, 3, 2, 1),
 ]
 
 

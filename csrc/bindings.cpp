@@ -925,6 +925,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     else if (which == "colred_chunks") { TORCH_CHECK(v >= 1 && v <= 65535, "colred_chunks"); pddl::g_colred_chunks = v; }
     else TORCH_CHECK(false, "unknown kernel knob ", which);
   });
+  // (kernel tests: did the forced tiling really run?)
+  m.def("wgrad_last_tiling", []() { return pddl::g_wgrad_last_tiling; });
   // (train/graph.py: is the stream's current capture still empty?) (hip error, capture status, #deps)
   m.def("stream_capture_deps", [](int64_t stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

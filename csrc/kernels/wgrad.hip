@@ -44,6 +44,15 @@ __device__ __forceinline__ v4bf tr_read(const char* p) {
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"((uint32_t)(uintptr_t)LDS_PTR(p)) : "memory");
   return r;
 }
+// The same read from an LDS byte address plus a compile-time offset (at most 65535: the
+// instruction's 16-bit offset field).
+template <int OFF>
+__device__ __forceinline__ v4bf tr_read_at(uint32_t addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
+  v4bf r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
+  return r;
+}
 
 // NSTAGE: LDS buffers.  2: the next m-tile's LDS-DMA overlaps this tile's MFMAs; 1: load ->
 // compute -> load in one buffer at half the LDS, so more blocks share a CU and overlap each
@@ -257,6 +266,40 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(WgradParams p, int m_per_
 // (padded / strided) gather decodes each row's im2col geometry arithmetically (magic-number
 // division) when its m-tile is staged: an ordinary global load of a row table would make the
 // compiler drain the LDS-DMA queue (vmcnt(0)) at its first use.
+//
+// Fragment pipeline: the transposed reads are asm the compiler cannot wait for per fragment, so
+// a phase that read its own fragments exposed their whole LDS round trip in front of its 16
+// MFMAs, on all 8 waves at once.  Instead phase P issues the reads of phase P+1 under its own
+// MFMAs (8 / 16 / 8 / 24 reads in q0..q3, one fragment per MFMA slot, into the register set
+// phase P does not use), and P+1 retires them (lgkmcnt(0), free by then) BEFORE arriving at its
+// first barrier.  Per phase: stage one half; lgkmcnt(0); counted vmcnt + barrier W(P); MFMAs of
+// P with the reads of P+1 between them; barrier T(P).
+//   RAW: the halves first read for phase P+1 are read after W(P), so W(P) waits (counted
+//   vmcnt, then the barrier publishes every wave's pieces) for the half(s) phase P+1 uses first
+//   -- the same wait the unpipelined loop placed there.  STAGGER (wave row wm = 1 one barrier
+//   behind): W(P) of the early row pairs with T(P-1) of the late row, which has only executed
+//   the wait of W(P-1); so under STAGGER every W waits one phase further ahead (and the
+//   prologue for halves 0..2).
+//   WAR (NQM = 2): half j is restaged by phase j+3 (LEAD 5, two buffers).  Its last reads are
+//   issued at the latest in phase j+1 (X cols 0-127, re-read for q3 during q2) and retired by
+//   every wave before it arrives at W(j+2); the staging wave has passed T(j+2), which every
+//   wave (the late row under STAGGER: W(j+2)) reaches after that.  So a half is restaged >= 1
+//   full phase after the wait that retired its last read.
+//
+// NQM: co-halves of the output tile.  2 is the 256 x 256 tile above.  1 (Cout <= 128: stage 3) is
+// a 128 (co) x 256 (k) tile on the same loop: three halves {G, X cols 0-127, X cols 128-255} and
+// two phases Q(0,0) Q(0,1) per m-tile, the G fragments read once and used by both.  Its 48 KiB
+// m-tile buffers form a ring of three (144 KiB; two blocks of 8 waves per CU would leave 128
+// registers a wave, fewer than accumulators plus two fragment sets need), staged two m-tiles
+// ahead: phase 2t stages G and the first X half of m-tile t+2, phase 2t+1 its second X half, so
+// a half again lands three phases before the wait that needs it.  RAW as above (W(2t) waits
+// for X cols 128-255 of t, W(2t+1) for G and X cols 0-127 of t+1; one phase further under
+// STAGGER).  WAR: m-tile t+2 overwrites m-tile t-1, whose last reads (X cols 128-255, issued in
+// phase 2t-2) every wave retired before arriving at W(2t-1), two barriers before the staging.
+// b2560, us, 128-wide kernel -> NQM = 1 (staggered): conv3 3x3 825 -> 774 (K = 1152 is 4.5
+// 256-wide tiles: a tenth of the MFMAs multiply padding), 3x3 stride 2 969 -> 866, 1x1 512>128
+// 519 -> 447.
+
 // Host-computed im2col stepping of wgrad8_kernel's generic gather (64 rows per m-tile).
 struct Wg8Geom {
   uint64_t mg_howo, mg_wo;   // magic divisors for the starting row of a split
@@ -265,18 +308,21 @@ struct Wg8Geom {
   uint32_t row_unit;         // bit r*S for every kernel row r
 };
 
-template <bool FAST, bool STAGGER>
+template <bool FAST, bool STAGGER, int NQM>
 __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per_split, Wg8Geom geo, int probe) {
-  constexpr int HALF = 16384, BUF = 4 * HALF, LEAD = 5;
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
+  constexpr int HPT = 2 + NQM;                // halves per m-tile
+  constexpr int NBUF = NQM == 2 ? 2 : 3;      // m-tile buffers in the ring
+  constexpr int HALF = 16384, BUF = HPT * HALF, LEAD = NQM == 2 ? 5 : 6;
+  constexpr int BCO = 128 * NQM;
+  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int tco = (p.Cout + 255) / 256, tk = (p.K + 255) / 256, ntiles = tco * tk;
+  const int tco = (p.Cout + BCO - 1) / BCO, tk = (p.K + 255) / 256, ntiles = tco * tk;
   const int splits = (p.M + m_per_split - 1) / m_per_split;
   const int wg = xcd_remap(blockIdx.x, ntiles * splits);
   const int tile = wg % ntiles, split = wg / ntiles;
-  const int co0 = (tile % tco) * 256, k0 = (tile / tco) * 256;
+  const int co0 = (tile % tco) * BCO, k0 = (tile / tco) * 256;
   const int mbeg = split * m_per_split;
   const int mend = min(p.M, mbeg + m_per_split);
   const int nit = (mend - mbeg + 63) / 64;
@@ -296,7 +342,7 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
     prow[i] = (2 * wave + i) * 4 + lrow;
     pch[i] = lpos ^ tr_swz(prow[i]);
   }
-  uint32_t g_off[2][2], x_off[2][2], x_bit[2][2];
+  uint32_t g_off[2][2], x_off[2][2], x_bit[2][2];   // (g_off[1]: NQM = 2 only)
   int x_delta2[2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
@@ -347,12 +393,13 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
       if (gho[i] >= p.Ho) { gho[i] -= p.Ho; gpix[i] += geo.carry_h; }
     }
   };
-  const int NH = 4 * nit;
-  // half-tile j = 4 t + part of m-tile t: part 0 G cols 0-127, 1 X cols 0-127, 2 X cols 128-255,
-  // 3 G cols 128-255 (first read in phases 0, 0, 1, 2 of the tile, as in igemm8_kernel)
-  auto stage_half = [&](int j, int part) {
-    const int mb = mbeg + (j >> 2) * 64;
-    char* base = smem + ((j >> 2) & 1) * BUF;
+  const int NH = HPT * nit;
+  // half-tile j = HPT t + part of m-tile t: part 0 G cols 0-127, 1 X cols 0-127, 2 X cols 128-255,
+  // 3 G cols 128-255 (first read in phases 0, 0, 1, 2 of the tile, as in igemm8_kernel); bo: the
+  // byte offset of m-tile ts's buffer in the ring
+  auto stage_half = [&](int ts, int part, uint32_t bo) {
+    const int mb = mbeg + ts * 64;
+    char* base = smem + bo;
     const bool full = mb + 64 <= mend;
     if (part == 0 || part == 3) {
       const int h = part == 0 ? 0 : 1;
@@ -378,18 +425,28 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
       }
     }
   };
+  // counted vmcnt (2 loads per half still allowed in flight), then the barrier.  In steady state
+  // the count is a compile-time constant of the phase; only while the staging runs out (the last
+  // m-tiles of a split, and the prologue of a short one) is it chosen at run time.
 #define WG8_WAIT_BARRIER(need, last)                                                              \
   {                                                                                               \
     const int after_ = (last) - (need);                                                           \
-    if (after_ >= 3) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");                \
+    if (after_ >= 5) asm volatile("s_waitcnt vmcnt(10)\n\ts_barrier" ::: "memory");               \
+    else if (after_ == 4) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");           \
+    else if (after_ == 3) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");           \
     else if (after_ == 2) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");           \
     else if (after_ == 1) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");           \
     else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                            \
   }
+#define WG8_WAIT_BARRIER_AT(need, nominal)                                                        \
+  {                                                                                               \
+    if (steady) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(2 * ((nominal) - (need))) : "memory"); \
+    else WG8_WAIT_BARRIER(need, NH - 1)                                                           \
+  }
 
-  v4f acc[2][2][4][2];
+  v4f acc[NQM][2][4][2];
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+  for (int a = 0; a < NQM; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -397,88 +454,173 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[a][b][i][j] = v4f{0.f, 0.f, 0.f, 0.f};
 
+  // prologue: halves 0 .. LEAD-1 (NQM = 1: m-tiles 0 and 1), then halves 0 and 1 (phase 0's;
+  // under STAGGER also half 2) landed and published
 #pragma unroll
   for (int j = 0; j < LEAD; ++j)
-    if (j < NH) stage_half(j, j & 3);
+    if (j < NH) stage_half(j / HPT, j % HPT, (j / HPT) * BUF);
   {
     const int last = (LEAD < NH ? LEAD : NH) - 1;
-    WG8_WAIT_BARRIER(1, last)
+    WG8_WAIT_BARRIER(STAGGER ? 2 : 1, last)
   }
   if (STAGGER && wm == 1) asm volatile("s_barrier" ::: "memory");
 
-  // fragment-read geometry (T10): group G = lane>>4 reads m-rows 8G + 4h + q, q = (lane&15)>>2,
-  // columns 4p..4p+3 of its 8-column chunk, p = lane&3
+  // fragment-read geometry (T10): group G = lane>>4 reads m-rows kh*32 + 8G + 4h + q,
+  // q = (lane&15)>>2, columns 4p..4p+3 of its 8-column chunk, p = lane&3.  tr_swz of that row
+  // depends on neither kh nor h, so a lane keeps one byte address per 16-column fragment (4 for
+  // G, 2 for X); kh, h and the half are the instruction's immediate offset and the buffer a
+  // scalar toggled per m-tile.
   const int Gq = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-  int roff[2][2], rsw[2][2];
+  uint32_t ga[4], xa[2];
+  {
+    const int row = 8 * Gq + qq;
+    const uint32_t ro = (uint32_t)(uintptr_t)LDS_PTR(smem) + row * 256 + (pp & 1) * 8;
 #pragma unroll
-  for (int kh = 0; kh < 2; ++kh)
+    for (int i = 0; i < 4; ++i) ga[i] = ro + (((wm * 8 + i * 2 + (pp >> 1)) ^ tr_swz(row)) << 4);
 #pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      const int row = kh * 32 + 8 * Gq + 4 * h2 + qq;
-      roff[kh][h2] = row * 256 + (pp & 1) * 8;
-      rsw[kh][h2] = tr_swz(row);
-    }
-  v8bf af[2][4], bfr[2][2];
-  for (int t = 0; t < nit; ++t) {
-    const char* buf = smem + (t & 1) * BUF;
+    for (int j = 0; j < 2; ++j) xa[j] = ro + (((wn * 4 + j * 2 + (pp >> 1)) ^ tr_swz(row)) << 4);
+  }
+  // Two fragment register sets per operand, so the set a phase prefetches into is never the one
+  // its MFMAs read.  NQM = 2: af[qm] holds the G fragments of co-half qm of the current m-tile,
+  // bfr[qn ^ tile parity] the X fragments of k-half qn.  NQM = 1: af[tile parity], bfr[qn].
+  v8bf af[2][2][4], bfr[2][2][2];
+  uint32_t boff = 0;   // byte offset of the current m-tile's buffer
+#define WG8_READ_G(d, part, bo, kh, i)                                                            \
+  {                                                                                               \
+    v4bf lo_ = (kh) == 0 ? tr_read_at<(part) * HALF>(ga[i] + (bo))                                \
+                         : tr_read_at<(part) * HALF + 8192>(ga[i] + (bo));                        \
+    v4bf hi_ = (kh) == 0 ? tr_read_at<(part) * HALF + 1024>(ga[i] + (bo))                         \
+                         : tr_read_at<(part) * HALF + 9216>(ga[i] + (bo));                        \
+    d = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);                                \
+  }
+#define WG8_READ_X(d, part, bo, kh, j)                                                            \
+  {                                                                                               \
+    v4bf lo_ = (kh) == 0 ? tr_read_at<(part) * HALF>(xa[j] + (bo))                                \
+                         : tr_read_at<(part) * HALF + 8192>(xa[j] + (bo));                        \
+    v4bf hi_ = (kh) == 0 ? tr_read_at<(part) * HALF + 1024>(xa[j] + (bo))                         \
+                         : tr_read_at<(part) * HALF + 9216>(xa[j] + (bo));                        \
+    d = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);                                \
+  }
+  // The asm reads are invisible to the compiler's wait insertion: the wait names every fragment
+  // register it retires, so no consumer (and no copy) of them can be scheduled above it.
+#define WG8_LANDED_G(s)                                                                           \
+  asm volatile("s_waitcnt lgkmcnt(0)"                                                             \
+               : "+v"(af[s][0][0]), "+v"(af[s][0][1]), "+v"(af[s][0][2]), "+v"(af[s][0][3]),      \
+                 "+v"(af[s][1][0]), "+v"(af[s][1][1]), "+v"(af[s][1][2]), "+v"(af[s][1][3])       \
+               :: "memory");
+#define WG8_LANDED_X(s)                                                                           \
+  asm volatile("s_waitcnt lgkmcnt(0)"                                                             \
+               : "+v"(bfr[s][0][0]), "+v"(bfr[s][0][1]), "+v"(bfr[s][1][0]), "+v"(bfr[s][1][1])   \
+               :: "memory");
+  // phase 0 of m-tile 0 (halves 0 and 1, published by the prologue barrier)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int qm = (q == 0 || q == 1) ? 0 : 1;
-      const int qn = (q == 0 || q == 3) ? 0 : 1;
-      const bool loadA = (q == 0 || q == 2), loadB = (q != 2);
-      if (loadB) {
-        const char* Xs = buf + (qn == 0 ? 1 : 2) * HALF;
+  for (int kh = 0; kh < 2; ++kh) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) WG8_READ_X(bfr[0][kh][j], 1, 0u, kh, j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) WG8_READ_G(af[0][kh][i], 0, 0u, kh, i)
+  }
+  for (int t2 = 0; t2 < nit; t2 += 2) {
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {   // (unrolled: the tile parity selects the register sets)
+      const int t = t2 + par;
+      if (t >= nit) break;
+      // (kept a run-time scalar: as a constant it would be folded into hoisted copies of every
+      // read address, more registers than the kernel has)
+      asm volatile("" : "+s"(boff));
+      const uint32_t nboff = boff + BUF == NBUF * BUF ? 0u : boff + BUF;            // m-tile t+1
+      const uint32_t nnboff = NQM == 2 ? boff : (boff == 0u ? 2u * BUF : boff - BUF);   // m-tile t+2
+#pragma unroll
+      for (int q = 0; q < 2 * NQM; ++q) {
+        const int qm = (q == 0 || q == 1) ? 0 : 1;
+        const int qn = (q == 0 || q == 3) ? 0 : 1;
+        const int gs = NQM == 2 ? qm : par;        // fragment register sets of this phase
+        const int xs = NQM == 2 ? qn ^ par : qn;
+        const bool more = t + 1 < nit;
+        // stage LEAD halves ahead: one half per phase (NQM = 2), or the G and first X half of
+        // m-tile t+2 in q0 and its second X half in q1 (NQM = 1)
+        // (js: the last half staged so far if the staging has not run out -- steady)
+        const int js = NQM == 2 ? 4 * t + q + LEAD : 3 * t + 7 + q;
+        const bool steady = js < NH;
+        if (steady) {
+          if (NQM == 2) stage_half(q == 3 ? t + 2 : t + 1, (q + LEAD) & 3, q == 3 ? nnboff : nboff);
+          else if (q == 0) { stage_half(t + 2, 0, nnboff); stage_half(t + 2, 1, nnboff); }
+          else stage_half(t + 2, 2, nnboff);
+        }
+        // this phase's fragments were read during the previous phase's MFMAs
+        if (q == 0 || q == 2) WG8_LANDED_G(gs)
+        if (q != 2) WG8_LANDED_X(xs)
+        // wait for the half(s) the NEXT phase's fragments come from, which this phase reads.
+        // NQM = 2: q0 -> part 2 of t; q1 -> part 3 of t; q2 -> none (part 1 again); q3 -> parts
+        // 0, 1 of t+1.  NQM = 1: q0 -> part 2 of t; q1 -> parts 0, 1 of t+1.  Staggered, the late
+        // wave row passes this barrier one phase later: every wait covers the phase after next.
+        if (NQM == 2 && !STAGGER) {
+          if (q == 0) WG8_WAIT_BARRIER_AT(4 * t + 2, js)
+          else if (q == 1) WG8_WAIT_BARRIER_AT(4 * t + 3, js)
+          else if (q == 3 && more) WG8_WAIT_BARRIER_AT(4 * t + 5, js)
+          else asm volatile("s_barrier" ::: "memory");
+        } else if (NQM == 2) {
+          if (q == 0) WG8_WAIT_BARRIER_AT(4 * t + 3, js)
+          else if (q == 2 && more) WG8_WAIT_BARRIER_AT(4 * t + 5, js)
+          else if (q == 3 && more) WG8_WAIT_BARRIER_AT(4 * t + 6, js)
+          else asm volatile("s_barrier" ::: "memory");
+        } else if (!STAGGER) {
+          if (q == 0) WG8_WAIT_BARRIER_AT(3 * t + 2, js)
+          else if (more) WG8_WAIT_BARRIER_AT(3 * t + 4, js)
+          else asm volatile("s_barrier" ::: "memory");
+        } else {
+          if (q == 0 && more) WG8_WAIT_BARRIER_AT(3 * t + 4, js)
+          else if (q == 0) WG8_WAIT_BARRIER_AT(3 * t + 2, js)
+          else if (more) WG8_WAIT_BARRIER_AT(3 * t + 5, js)
+          else asm volatile("s_barrier" ::: "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+        // 16 MFMAs, with the next phase's fragment reads issued one fragment per MFMA from the
+        // first on (NQM = 2: 8 / 16 / 8 / 24 reads, NQM = 1: 8 / 24), so their latency hides under
+        // this phase.  After the last m-tile the last phase reads the next buffer's stale tile
+        // into registers nobody uses.
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int ch = wn * 4 + j * 2 + (pp >> 1);
-            v4bf lo = tr_read(Xs + roff[kh][0] + ((ch ^ rsw[kh][0]) << 4));
-            v4bf hi = tr_read(Xs + roff[kh][1] + ((ch ^ rsw[kh][1]) << 4));
-            bfr[kh][j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          }
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              acc[qm][qn][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[gs][kh][i], bfr[xs][kh][j], acc[qm][qn][i][j], 0, 0, 0);
+              const int n = (kh * 4 + i) * 2 + j;
+              const int f = n & 7;   // slot within this k-half's 8 MFMAs
+              if (q == 0 && n < 4) WG8_READ_X(bfr[xs ^ 1][n >> 1][n & 1], 2, boff, n >> 1, n & 1)
+              if (NQM == 2) {
+                if (q == 1 && f < 4) WG8_READ_G(af[1][kh][f], 3, boff, kh, f)
+                if (q == 2 && n < 4) WG8_READ_X(bfr[xs ^ 1][n >> 1][n & 1], 1, boff, n >> 1, n & 1)
+              }
+              if (q == 2 * NQM - 1 && f < 2) WG8_READ_X(bfr[xs ^ 1][kh][f], 1, nboff, kh, f)
+              if (q == 2 * NQM - 1 && f >= 2 && f < 6)
+                WG8_READ_G(af[NQM == 2 ? 0 : par ^ 1][kh][f - 2], 0, nboff, kh, f - 2)
+              __builtin_amdgcn_sched_barrier(0);
+            }
+        __builtin_amdgcn_s_setprio(0);
+        asm volatile("s_barrier" ::: "memory");
       }
-      __builtin_amdgcn_sched_barrier(0);
-      if (loadA) {
-        const char* Gs = buf + (qm == 0 ? 0 : 3) * HALF;
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int ch = wm * 8 + i * 2 + (pp >> 1);
-            v4bf lo = tr_read(Gs + roff[kh][0] + ((ch ^ rsw[kh][0]) << 4));
-            v4bf hi = tr_read(Gs + roff[kh][1] + ((ch ^ rsw[kh][1]) << 4));
-            af[kh][i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          }
-      }
-      const int js = 4 * t + q + LEAD;
-      if (js < NH) stage_half(js, (q + LEAD) & 3);
-      const int last = (js < NH ? js : NH - 1);
-      if (q == 0) WG8_WAIT_BARRIER(4 * t + 2, last)
-      else if (q == 1) WG8_WAIT_BARRIER(4 * t + 3, last)
-      else if (q == 3 && t + 1 < nit) WG8_WAIT_BARRIER(4 * t + 5, last)
-      else asm volatile("s_barrier" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the asm fragment reads)
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[qm][qn][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kh][i], bfr[kh][j], acc[qm][qn][i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_barrier" ::: "memory");
+      boff = nboff;
     }
   }
+  // the last phase's reads land in registers the compiler must not reuse before they have
+  WG8_LANDED_G(0)
+  if (NQM == 1) WG8_LANDED_G(1)
+  WG8_LANDED_X(0)
+  WG8_LANDED_X(1)
 #undef WG8_WAIT_BARRIER
+#undef WG8_WAIT_BARRIER_AT
+#undef WG8_READ_G
+#undef WG8_READ_X
+#undef WG8_LANDED_G
+#undef WG8_LANDED_X
   if (STAGGER && wm == 0) asm volatile("s_barrier" ::: "memory");
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
   if (probe & 1) {   // (timing probe only: main loop without the atomic epilogue)
-    if (acc[0][0][0][0][0] == 12345.f && acc[1][1][3][1][3] == 54321.f) p.dw[tid] = 0.f;
+    if (acc[0][0][0][0][0] == 12345.f && acc[NQM - 1][1][3][1][3] == 54321.f) p.dw[tid] = 0.f;
     return;
   }
 
@@ -486,9 +628,14 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
   // then row-contiguous atomics: 2 rows of 32 floats (2 x 128 B) per wave instruction
   constexpr int EPI_LD = 36;
   float* stage = reinterpret_cast<float*>(smem) + wave * (32 * EPI_LD);
-  const int rsub = lane >> 5, cl = lane & 31;
+  // (the lane id goes through an empty asm so its derived indices are computed here, not kept
+  // in registers across the main loop, which has none to spare)
+  int elane = tid;
+  asm volatile("" : "+v"(elane));
+  elane &= 63;
+  const int rsub = elane >> 5, cl = elane & 31;
 #pragma unroll
-  for (int qm = 0; qm < 2; ++qm)
+  for (int qm = 0; qm < NQM; ++qm)
 #pragma unroll
     for (int qn = 0; qn < 2; ++qn) {
       const int kcol = k0 + qn * 128 + wn * 32 + cl;
@@ -500,7 +647,7 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(WgradParams p, int m_per
           for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
-              stage[(i2 * 16 + (lane >> 4) * 4 + jj) * EPI_LD + j * 16 + (lane & 15)] = acc[qm][qn][pass * 2 + i2][j][jj];
+              stage[(i2 * 16 + (elane >> 4) * 4 + jj) * EPI_LD + j * 16 + (elane & 15)] = acc[qm][qn][pass * 2 + i2][j][jj];
         __syncthreads();
         if (kcol < p.K) {
           for (int r = 0; r < 32; r += 2) {
@@ -560,10 +707,15 @@ int g_wgrad1 = 1;          // LDS stages of the 128/64-wide wgrad kernel: 1 = si
                            // long-reduction direct layers and grids of at most one block per CU (1x1 / stem window, M >= 2M rows: stage-2
                            // 1x1s -4..-12 %, stem -8 %, 3x3 and stage 3+ +8..+13 % with 2 stages;
                            // per-layer A/B at b1024), 0 = 2 stages everywhere, 2 = single everywhere
-int g_wgrad8 = 1;          // 8-phase 256x256 wgrad8_kernel for Cout >= 256, K >= 256: 0 off, 1 on where its grid
-                           // each block's reduction amortises its atomic burst (wgrad_launch_one), 2 with the wave-row stagger (slower here);
+int g_wgrad8 = 2;          // 8-phase wgrad8_kernel (256x256 tiles for Cout >= 256, 128x256 for 64 < Cout <= 128), K >= 256: 0 off; 1 on where each block's
+                           // reduction amortises its atomic burst (wgrad_launch_one); 2 (default) the same with the
+                           // wave-row stagger.  With the fragment reads prefetched a phase ahead the stagger wins on
+                           // every layer class (b2560, us, unpipelined / 1 / 2: conv4 3x3 656 / 625 / 576, conv5 3x3
+                           // 657 / 606 / 555, 1x1 1024>256 319 / 304 / 268, 2048>512 293 / 290 / 246, 256>1024
+                           // 318 / 297 / 269, conv3 3x3 (128x256 tile) 825 / 793 / 774; before the prefetch it lost
+                           // 1-3 %: profiles/wgrad8_pipeline_b2560.txt);
                            // +8 (probe): skip the atomic epilogue; +16: whatever the grid
-
+int g_wgrad_last_tiling = 0;
 int g_wgrad8_min_rows = 512;    // wgrad8 m-reduction split: at least this many rows per split (knob;
                                 // b32: 1024 -> 512 rows 5.32 -> 5.06 ms/step, 256: 5.26)
 
@@ -631,7 +783,9 @@ static const char* wgrad_launch_one(const WgradParams& pin, hipStream_t stream) 
 
   // 8-phase 256x256 tiles (one block per CU): split the m reduction so tiles x splits ~ one
   // round of CUs, each split at least g_wgrad8_min_rows rows.
-  const int nt8 = ((p.Cout + 255) / 256) * ((p.K + 255) / 256);
+  // Cout <= 128 takes the one-co-half form (128 x 256 tiles, NQM = 1).
+  const bool narrow = p.Cout <= 128;
+  const int nt8 = ((p.Cout + (narrow ? 127 : 255)) / (narrow ? 128 : 256)) * ((p.K + 255) / 256);
   int sp = (num_cus() + nt8 / 2) / nt8;
   const int cap = (p.M + g_wgrad8_min_rows - 1) / g_wgrad8_min_rows;
   if (sp > cap) sp = cap;
@@ -639,7 +793,7 @@ static const char* wgrad_launch_one(const WgradParams& pin, hipStream_t stream) 
   const int mps8 = ((p.M + sp - 1) / sp + 63) / 64 * 64;
   sp = (p.M + mps8 - 1) / mps8;
   // (the generic gather steps pixel indices through 24-bit multiplies: < 2^22 pixels per split)
-  const bool elig8 = g_wgrad8 && p.Cout >= 256 && p.K >= 256 && !window && p.splits <= 0 && span_ok(mps8) &&
+  const bool elig8 = g_wgrad8 && p.Cout > 64 && (narrow || p.Cout >= 256) && p.K >= 256 && !window && p.splits <= 0 && span_ok(mps8) &&
                      (fast || (span_pix(mps8) < (1L << 22) && 2L * p.C < (1L << 23)));
   // Which tiling.  Every 8-phase block ends with a burst of fp32 atomics of its 256 KiB partial
   // tile, and one round of blocks (one per CU) is ~64 MiB of atomics at the chip's ~1.3 TB/s
@@ -655,6 +809,7 @@ static const char* wgrad_launch_one(const WgradParams& pin, hipStream_t stream) 
     const double F = 2.0 * p.M * (double)p.Cout * p.K, w8 = (double)nt8 * sp;
     use8 = (g_wgrad8 & 16) || !plan1_ok || (F >= 4e8 * w8 && 2 * w8 >= num_cus());
   }
+  g_wgrad_last_tiling = use8 ? 1000 + (narrow ? 128 : 256) : BM;
   if (use8) {
     const int mps = mps8;
     Wg8Geom geo{};
@@ -669,13 +824,15 @@ static const char* wgrad_launch_one(const WgradParams& pin, hipStream_t stream) 
       geo.carry_h = p.H * p.W - p.Ho * p.stride * p.W;
       for (int r = 0; r < p.R; ++r) geo.row_unit |= 1u << (r * p.S);
     }
-    if ((g_wgrad8 & 7) == 2) {
-      if (fast) hipLaunchKernelGGL((wgrad8_kernel<true, true>), dim3(nt8 * sp), dim3(512), 0, stream, p, mps, geo, g_wgrad8 >> 3);
-      else hipLaunchKernelGGL((wgrad8_kernel<false, true>), dim3(nt8 * sp), dim3(512), 0, stream, p, mps, geo, g_wgrad8 >> 3);
-    } else {
-      if (fast) hipLaunchKernelGGL((wgrad8_kernel<true, false>), dim3(nt8 * sp), dim3(512), 0, stream, p, mps, geo, g_wgrad8 >> 3);
-      else hipLaunchKernelGGL((wgrad8_kernel<false, false>), dim3(nt8 * sp), dim3(512), 0, stream, p, mps, geo, g_wgrad8 >> 3);
-    }
+    const bool stagger = (g_wgrad8 & 7) == 2;
+#define WG8_LAUNCH(F_, S_, Q_) \
+  hipLaunchKernelGGL((wgrad8_kernel<F_, S_, Q_>), dim3(nt8 * sp), dim3(512), 0, stream, p, mps, geo, g_wgrad8 >> 3);
+#define WG8_LAUNCH_Q(Q_)                                                \
+  if (stagger) { if (fast) WG8_LAUNCH(true, true, Q_) else WG8_LAUNCH(false, true, Q_) } \
+  else { if (fast) WG8_LAUNCH(true, false, Q_) else WG8_LAUNCH(false, false, Q_) }
+    if (narrow) { WG8_LAUNCH_Q(1) } else { WG8_LAUNCH_Q(2) }
+#undef WG8_LAUNCH_Q
+#undef WG8_LAUNCH
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }
