@@ -739,6 +739,51 @@ void sgd(Tensor p, Tensor g, Tensor mom, double lr, double momentum, double wd, 
                       nesterov ? 1 : 0, (float)gscale, of32p(hs), cur_stream()),
      "sgd");
 }
+void opt_hparams_sched(Tensor hs, double b1, double b2, bool adam) {
+  PCHECK(hs.is_cuda() && hs.scalar_type() == torch::kFloat32 && hs.numel() >= 8 && hs.is_contiguous(),
+         "scheduled hparams: device float[>=8]");
+  ok(pddl::opt_hparams_sched_launch(f32p(hs), (float)b1, (float)b2, adam ? 1 : 0, cur_stream()), "opt_hparams_sched");
+}
+const pddl::LarsSeg* lars_host_table(const Tensor& table_host, int64_t& nseg) {
+  PCHECK(!table_host.is_cuda() && table_host.scalar_type() == torch::kInt32 && table_host.is_contiguous() &&
+             table_host.dim() == 2 && table_host.size(1) == 4,
+         "lars: host table is int32 [nseg][4] = {offset, size, adapt, chunk0}");
+  static_assert(sizeof(pddl::LarsSeg) == 4 * sizeof(int32_t), "LarsSeg is four ints");
+  nseg = table_host.size(0);
+  return reinterpret_cast<const pddl::LarsSeg*>(table_host.data_ptr<int32_t>());
+}
+// Number of chunks of a host segment table at this chunk size (raises on a malformed table).
+int64_t lars_chunks(Tensor table_host, int64_t n, int64_t chunk) {
+  int64_t nseg;
+  const pddl::LarsSeg* segs = lars_host_table(table_host, nseg);
+  PCHECK(chunk > 0 && chunk <= INT32_MAX, "lars: chunk out of range");
+  const char* err;
+  const long c = pddl::lars_check_table(segs, (int)nseg, n, (int)chunk, &err);
+  ok(err, "lars");
+  return c;
+}
+void lars(Tensor p, Tensor g, Tensor mom, Tensor table, Tensor table_host, int64_t chunk, Tensor partials,
+          Tensor ratios, double lr, double momentum, double wd, double eta, double eps, double gscale, OptT hs) {
+  int64_t nseg;
+  const pddl::LarsSeg* segs = lars_host_table(table_host, nseg);
+  PCHECK(table.is_cuda() && table.scalar_type() == torch::kInt32 && table.is_contiguous() &&
+             table.numel() == table_host.numel(),
+         "lars: device table is the int32 GPU copy of the host table");
+  PCHECK(p.is_contiguous() && g.is_contiguous() && mom.is_contiguous() && g.numel() >= p.numel() &&
+             mom.numel() >= p.numel() && p.numel() <= INT32_MAX,
+         "lars: p, g, momentum contiguous, g and momentum at least as long as p");
+  PCHECK(partials.is_contiguous() && ratios.is_contiguous() && chunk > 0 && chunk <= INT32_MAX, "lars: buffers");
+  PCHECK(!hs.has_value() || hs->numel() >= 3, "lars: hs is device float[>=3]");
+  PCHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
+             reinterpret_cast<uintptr_t>(mom.data_ptr()) % 16 == 0 &&
+             reinterpret_cast<uintptr_t>(partials.data_ptr()) % 8 == 0,
+         "lars: p, g, momentum 16-byte aligned");
+  ok(pddl::lars_launch(f32p(p), f32p(g), f32p(mom), p.numel(), reinterpret_cast<const pddl::LarsSeg*>(table.data_ptr()),
+                       segs, (int)nseg, (int)chunk, f32p(partials), partials.numel(), f32p(ratios), ratios.numel(),
+                       (float)lr, (float)momentum, (float)wd, (float)eta, (float)eps, (float)gscale, of32p(hs),
+                       cur_stream()),
+     "lars");
+}
 void scale_(Tensor x, double a) { ok(pddl::scale_launch(f32p(x), x.numel(), (float)a, cur_stream()), "scale"); }
 void cast_bf16(Tensor x, Tensor y) { ok(pddl::cast_bf16_launch(f32p(x), bfpm(y), x.numel(), cur_stream()), "cast"); }
 void cast_f32(Tensor x, Tensor y) { ok(pddl::cast_f32_launch(bfp(x), f32p(y), x.numel(), cur_stream()), "cast"); }
@@ -959,6 +1004,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("opt_hparams", &opt_hparams, REL);
   m.def("adam", &adam, REL);
   m.def("sgd", &sgd, REL);
+  m.def("opt_hparams_sched", &opt_hparams_sched, REL);
+  m.def("lars", &lars, REL, py::arg("p"), py::arg("g"), py::arg("momentum"), py::arg("table"), py::arg("table_host"),
+        py::arg("chunk"), py::arg("partials"), py::arg("ratios"), py::arg("lr"), py::arg("mu"), py::arg("wd"),
+        py::arg("eta"), py::arg("eps"), py::arg("gscale"), py::arg("hs") = none);
+  m.def("lars_chunks", &lars_chunks, REL);
+  m.attr("LARS_DEFAULT_CHUNK") = (int)pddl::kLarsDefaultChunk;
   m.def("scale_", &scale_, REL);
   m.def("cast_bf16", &cast_bf16, REL);
   m.def("cast_f32", &cast_f32, REL);

@@ -366,6 +366,21 @@ const char* adam_launch(float* p, const float* g, float* m, float* v, long n, fl
                         float eps, float gscale, const float* hs, hipStream_t s);
 const char* sgd_launch(float* p, const float* g, float* mom, long n, float lr, float momentum, float wd,
                        int nesterov, float gscale, const float* hs, hipStream_t s);
+// Scheduled step hyper-parameters: hs = {t, lr, lr_t, lr_sched, warmup_steps, total_steps, end_lr, -}.
+const char* opt_hparams_sched_launch(float* hs, float b1, float b2, int adam, hipStream_t s);
+// LARS.  One table entry per segment of the trainable prefix, ascending and disjoint; offsets and
+// sizes are multiples of 4 floats.  chunk0 is the running count of ceil(size / chunk) over the
+// entries before this one: chunk c of the segment is block chunk0 + c of both passes and owns
+// partials[chunk0 + c] = (sum w^2, sum (gs g)^2).  adapt = 0: plain momentum update, no decay.
+struct LarsSeg {
+  int off, size, adapt, chunk0;
+};
+constexpr int kLarsDefaultChunk = 16384;
+long lars_check_table(const LarsSeg* segs, int nseg, long n, int chunk, const char** err);
+const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSeg* segs_dev, const LarsSeg* segs_host,
+                        int nseg, int chunk, float* partials, long partials_floats, float* ratios, long ratios_floats,
+                        float lr, float momentum, float wd, float eta, float eps, float gscale, const float* hs,
+                        hipStream_t s);
 const char* adam_bf16_wire_launch(float* p, const uint16_t* g, float* m, float* v, uint16_t* snap, long n, float lr_t,
                                   float b1, float b2, float eps, hipStream_t s);
 const char* scale_launch(float* x, long n, float a, hipStream_t s);

@@ -8,6 +8,8 @@
 // SGD with momentum follows keras.optimizers.SGD:  v = mu v - lr g;  p += v  (Nesterov:
 // p += mu v - lr g), with optional L2 weight decay folded into g.
 // One launch updates all 25.6M parameters; 16-byte loads/stores per lane.
+// LARS (large global batches) is momentum SGD with a per-layer trust ratio: two launches over a
+// segment table of the same buffer, a norm pass and an update pass (below).
 #include "common.h"
 #include "kernels.h"
 
@@ -96,6 +98,133 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   }
 }
 
+// Scheduled form of opt_hparams_kernel.  hs = {t, lr, lr_t, lr_sched, warmup_steps, total_steps,
+// end_lr, -}: linear warm-up from 0 to lr over warmup_steps, polynomial decay (power 2) to end_lr
+// at total_steps, end_lr after that.  One thread per step, so the arithmetic is done in double:
+// the fp32 result is then the correctly rounded host formula, whatever powf would have lost in
+// 1 - b2^t at small t.  hs[3] keeps the scheduled rate before Adam's bias correction.
+__global__ void opt_hparams_sched_kernel(float* hs, float b1, float b2, int adam) {
+  const float t = hs[0] + 1.f;
+  hs[0] = t;
+  const double lr = hs[1], wu = hs[4], tot = hs[5], end_lr = hs[6], td = t;
+  double s;
+  if (td <= wu) {
+    s = lr * td / wu;
+  } else if (td < tot) {
+    const double rem = (tot - td) / (tot - wu);
+    s = end_lr + (lr - end_lr) * rem * rem;
+  } else {
+    s = end_lr;
+  }
+  hs[3] = (float)s;
+  hs[2] = (float)(adam ? s * sqrt(1.0 - pow((double)b2, td)) / (1.0 - pow((double)b1, td)) : s);
+}
+
+// ---- LARS (You et al.; the MLPerf ResNet-50 form) over the segment table -------------------
+// Every replica runs this on identical all-reduced gradients and nothing re-synchronises the
+// parameters afterwards, so the norms must come out bit-identical on every replica and every
+// run: no atomics, no arrival-order combine.  Chunk c of segment s is summed by one block in a
+// fixed thread -> wave -> block tree, and every block of the update pass folds its segment's
+// partials in the same fixed order (lane j takes partials j, j+256, ... in index order, then
+// the same tree).  The order is a pure function of the segment table and the chunk size.
+
+// Segment of global chunk b: the last s with segs[s].chunk0 <= b (chunk0 ascends from 0).
+__device__ __forceinline__ int lars_find_seg(const LarsSeg* __restrict__ segs, int nseg, int b) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (segs[mid].chunk0 <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Block-wide sums of (a, b) in a fixed order; the result is valid in every thread.
+__device__ __forceinline__ float2 lars_block_sum2(float a, float b, float2* red) {
+  a = warp_sum(a);
+  b = warp_sum(b);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();   // (red may still be read from a previous call)
+  if ((threadIdx.x & 63) == 0) red[wave] = make_float2(a, b);
+  __syncthreads();
+  float2 r = red[0];
+#pragma unroll
+  for (int w = 1; w < 4; w++) { r.x += red[w].x; r.y += red[w].y; }
+  return r;
+}
+
+__global__ __launch_bounds__(256) void lars_norm_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                        const LarsSeg* __restrict__ segs, int nseg, int chunk,
+                                                        float gs, float2* __restrict__ partials) {
+  __shared__ float2 red[4];
+  const int b = blockIdx.x;
+  const LarsSeg sg = segs[lars_find_seg(segs, nseg, b)];
+  if (!sg.adapt) return;   // (its partials are never read)
+  const long start = (long)(b - sg.chunk0) * chunk;
+  const int n4 = (int)lmin((long)chunk, sg.size - start) >> 2;
+  const float4* p4 = reinterpret_cast<const float4*>(p + sg.off + start);
+  const float4* g4 = reinterpret_cast<const float4*>(g + sg.off + start);
+  float sw = 0.f, sgg = 0.f;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const float4 w = p4[i];
+    float4 d = g4[i];
+    d.x *= gs; d.y *= gs; d.z *= gs; d.w *= gs;
+    sw += (w.x * w.x + w.y * w.y) + (w.z * w.z + w.w * w.w);
+    sgg += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+  }
+  const float2 r = lars_block_sum2(sw, sgg, red);
+  if (threadIdx.x == 0) partials[b] = r;
+}
+
+__global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ v, const LarsSeg* __restrict__ segs,
+                                                          int nseg, int chunk, const float2* __restrict__ partials,
+                                                          float* __restrict__ ratios, float lr, float mu, float wd,
+                                                          float eta, float eps, float gs,
+                                                          const float* __restrict__ hs) {
+  __shared__ float2 red[4];
+  if (hs) lr = hs[2];
+  const int b = blockIdx.x;
+  const int s = lars_find_seg(segs, nseg, b);
+  const LarsSeg sg = segs[s];
+  float ratio = 1.f;
+  if (sg.adapt) {
+    const int m = (int)((sg.size + (long)chunk - 1) / chunk);
+    float sw = 0.f, sgg = 0.f;
+    for (int j = threadIdx.x; j < m; j += 256) {
+      const float2 q = partials[sg.chunk0 + j];
+      sw += q.x;
+      sgg += q.y;
+    }
+    const float2 r = lars_block_sum2(sw, sgg, red);
+    const float wn = sqrtf(r.x), gn = sqrtf(r.y);
+    if (wn > 0.f && gn > 0.f) ratio = eta * wn / (gn + wd * wn + eps);
+  } else {
+    wd = 0.f;   // biases and BN parameters: no decay, no adaptation
+  }
+  if (b == sg.chunk0 && threadIdx.x == 0) ratios[s] = ratio;
+  const float step = lr * ratio;
+  const long start = (long)(b - sg.chunk0) * chunk;
+  const int n4 = (int)lmin((long)chunk, sg.size - start) >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p + sg.off + start);
+  const float4* g4 = reinterpret_cast<const float4*>(g + sg.off + start);
+  float4* v4 = reinterpret_cast<float4*>(v + sg.off + start);
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 pp = p4[i];
+    const float4 gg = g4[i];
+    float4 vv = v4[i];
+#define LARS1(c)                                              \
+  {                                                           \
+    const float u = gg.c * gs + wd * pp.c;                    \
+    vv.c = mu * vv.c + step * u;                              \
+    pp.c -= vv.c;                                             \
+  }
+    LARS1(x) LARS1(y) LARS1(z) LARS1(w)
+#undef LARS1
+    p4[i] = pp;
+    v4[i] = vv;
+  }
+}
+
 __global__ void scale_kernel(float* __restrict__ x, long n, float a) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
 }
@@ -129,6 +258,46 @@ const char* sgd_launch(float* p, const float* g, float* mom, long n, float lr, f
   if (n % 4) return "sgd: n must be a multiple of 4";
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_of(n / 4)), dim3(256), 0, s, p, g, mom, n / 4, lr, momentum, wd, nesterov,
                      gscale, hs);
+  LAUNCH_RET
+}
+const char* opt_hparams_sched_launch(float* hs, float b1, float b2, int adam, hipStream_t s) {
+  hipLaunchKernelGGL(opt_hparams_sched_kernel, dim3(1), dim3(1), 0, s, hs, b1, b2, adam);
+  LAUNCH_RET
+}
+// Checks the host copy of the segment table (the device copy holds the same bytes) and returns
+// the number of chunks, or -1 with *err set.
+long lars_check_table(const LarsSeg* segs, int nseg, long n, int chunk, const char** err) {
+  *err = nullptr;
+  if (nseg < 1) { *err = "lars: empty segment table"; return -1; }
+  if (chunk < 4 || chunk % 4) { *err = "lars: chunk must be a positive multiple of 4"; return -1; }
+  long chunks = 0, end = 0;
+  for (int i = 0; i < nseg; i++) {
+    const LarsSeg& sg = segs[i];
+    if (sg.off % 4 || sg.size % 4) { *err = "lars: segment offsets and sizes must be multiples of 4"; return -1; }
+    if (sg.size <= 0 || sg.off < end || (long)sg.off + sg.size > n) {
+      *err = "lars: segments must be non-empty, ascending, disjoint and inside the buffer";
+      return -1;
+    }
+    if (sg.chunk0 != chunks) { *err = "lars: chunk0 is not the running chunk count for this chunk size"; return -1; }
+    end = (long)sg.off + sg.size;
+    chunks += (sg.size + (long)chunk - 1) / chunk;
+    if (chunks > 0x7fffffffL) { *err = "lars: too many chunks"; return -1; }
+  }
+  return chunks;
+}
+const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSeg* segs_dev, const LarsSeg* segs_host,
+                        int nseg, int chunk, float* partials, long partials_floats, float* ratios, long ratios_floats,
+                        float lr, float momentum, float wd, float eta, float eps, float gscale, const float* hs,
+                        hipStream_t s) {
+  const char* err;
+  const long chunks = lars_check_table(segs_host, nseg, n, chunk, &err);
+  if (chunks < 0) return err;
+  if (partials_floats < 2 * chunks) return "lars: partials buffer smaller than 2 floats per chunk";
+  if (ratios_floats < nseg) return "lars: ratio buffer smaller than the segment table";
+  hipLaunchKernelGGL(lars_norm_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, segs_dev, nseg, chunk, gscale,
+                     reinterpret_cast<float2*>(partials));
+  hipLaunchKernelGGL(lars_update_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, v, segs_dev, nseg, chunk,
+                     reinterpret_cast<const float2*>(partials), ratios, lr, momentum, wd, eta, eps, gscale, hs);
   LAUNCH_RET
 }
 const char* scale_launch(float* x, long n, float a, hipStream_t s) {

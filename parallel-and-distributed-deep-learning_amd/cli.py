@@ -49,6 +49,11 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
             sys.stderr.write("--evaluate is not supported for --strategy ps: score the PS checkpoint with the single "
                              "or mirrored script (--evaluate --weights <the final PS checkpoint>)\n")
             return 2
+        if cfg.optimizer == "lars" or cfg.lr_schedule == "poly":
+            what = "--optimizer lars" if cfg.optimizer == "lars" else "--lr-schedule poly"
+            sys.stderr.write(f"{what} is not supported for --strategy ps: the parameter servers apply Adam at a "
+                             "host-set rate (use the mirrored, multiworker or horovod script for large batches)\n")
+            return 2
         from .parallel.parameter_server import run_ps_job
         return run_ps_job(cfg)
     if cfg.roctx:
@@ -71,7 +76,8 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
     rs = getattr(strategy, "resume_state", None)
     if rs:          # --resume of a periodic checkpoint: epochs, LR and callback state continue
         initial_epoch = int(rs.get("epoch", 0))
-        trainer.set_lr(float(rs.get("lr", trainer.lr)))
+        if cfg.lr_schedule != "poly":   # (poly: the rate follows the restored optimizer iteration count)
+            trainer.set_lr(float(rs.get("lr", trainer.lr)))
         trainer.resume_state = rs
         if strategy.is_chief:
             print(f"Resuming after epoch {initial_epoch} at lr {trainer.lr:.4g}", flush=True)

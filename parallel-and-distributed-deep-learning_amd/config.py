@@ -46,6 +46,8 @@ class TrainConfig:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-7
+    lars_eta: float = 1e-3                         # LARS trust coefficient
+    lars_eps: float = 0.0                          # LARS: added to the trust ratio's denominator
     # training loop
     epochs: int = 50                               # imagenet-resnet50.py:67
     verbose: int = 2
@@ -55,6 +57,9 @@ class TrainConfig:
     early_stop_patience: int = 10                  # EarlyStopping (imagenet-resnet50.py:65)
     early_stop_min_delta: float = 1e-3
     warmup_epochs: int = 0                         # hvd LearningRateWarmupCallback (hvd.py:115): 3
+    lr_schedule: str = "plateau"                   # plateau (the reference's callbacks) | poly: per-step warm-up
+                                                   # over warmup_epochs + power-2 decay to lr_end, on the device
+    lr_end: float = 1e-4                           # poly: the rate at and after the last step
     # distribution
     strategy: str = "single"                       # single | mirrored | multiworker | horovod | ps
     bucket_mb: float = 32.0                        # gradient bucket size (7-link xGMI tuned); <= 0: autotune
@@ -139,9 +144,18 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--image-size", type=int, dest="image_size")
     a("--precision", choices=["bf16", "fp32"])
     a("--bn-mode", choices=["frozen", "train"], dest="bn_mode")
-    a("--optimizer", choices=["adam", "sgd"])
+    a("--optimizer", choices=["adam", "sgd", "lars"])
     a("--lr", type=float)
     a("--momentum", type=float)
+    a("--weight-decay", type=float, dest="weight_decay")
+    a("--nesterov", action="store_true", default=None, help="SGD: Nesterov momentum")
+    a("--lars-eta", type=float, dest="lars_eta", help="LARS trust coefficient")
+    a("--lars-eps", type=float, dest="lars_eps", help="LARS: added to the trust ratio's denominator")
+    a("--lr-schedule", choices=["plateau", "poly"], dest="lr_schedule",
+      help="plateau: ReduceLROnPlateau (+ the Horovod warm-up); poly: per-step linear warm-up over "
+           "--warmup-epochs, then power-2 decay to --lr-end at the last step, computed on the device")
+    a("--lr-end", type=float, dest="lr_end")
+    a("--warmup-epochs", type=int, dest="warmup_epochs")
     a("--data", type=str)
     a("--cache", type=str, dest="data_cache")
     a("--steps-per-epoch", type=int, dest="steps_per_epoch")

@@ -173,7 +173,8 @@ class Strategy:
         eng.init(seed=self.cfg.seed)
         opt = make_optimizer(self.cfg.optimizer, eng, lr=self.cfg.lr, momentum=self.cfg.momentum,
                              nesterov=self.cfg.nesterov, weight_decay=self.cfg.weight_decay, beta1=self.cfg.beta1,
-                             beta2=self.cfg.beta2, eps=self.cfg.adam_eps)
+                             beta2=self.cfg.beta2, eps=self.cfg.adam_eps, lars_eta=self.cfg.lars_eta,
+                             lars_eps=self.cfg.lars_eps)
         return eng, opt
 
     def _build(self, trainer):
@@ -223,6 +224,11 @@ class Strategy:
     def set_lr(self, lr: float):
         for _, opt in self._replicas():
             opt.lr = lr
+
+    def set_schedule(self, warmup_steps: int, total_steps: int, end_lr: float):
+        """--lr-schedule poly: every replica's optimizer derives the step's rate on the device."""
+        for _, opt in self._replicas():
+            opt.set_schedule(warmup_steps, total_steps, end_lr)
 
     def eval_step(self, images, labels, top5: bool = False):
         """[loss sum, top-1 hits] of the batch, or with top5 [loss sum, top-1 hits, top-5 hits]."""
@@ -582,7 +588,8 @@ class _LocalReplicas:
             eng = build_engine(cfg, d, cap, graphed=graphed)
             eng.init(seed=cfg.seed)
             opt = make_optimizer(cfg.optimizer, eng, lr=cfg.lr, momentum=cfg.momentum, nesterov=cfg.nesterov,
-                                 weight_decay=cfg.weight_decay, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.adam_eps)
+                                 weight_decay=cfg.weight_decay, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.adam_eps,
+                                 lars_eta=cfg.lars_eta, lars_eps=cfg.lars_eps)
             self.replicas.append((eng, opt))
             self.augs.append(Augment(cfg, d, cfg.seed + 7919 * (global_rank_base + i)))
         self.comm = None

@@ -2,7 +2,9 @@
 
 Adam reproduces TF/Keras `ResourceApplyAdam` (epsilon-hat form; imagenet-resnet50.py:62),
 SGD reproduces `keras.optimizers.SGD(momentum, nesterov)` — the north-star optimizer
-(BASELINE.json).  On CPU the same update runs as torch ops (reference semantics).
+(BASELINE.json).  LARS (You et al., the MLPerf ResNet-50 form) is the large-batch optimizer:
+momentum SGD whose step is scaled per layer by a trust ratio, in two launches over a segment
+table of the flat buffer.  On CPU the same update runs as torch ops (reference semantics).
 """
 from __future__ import annotations
 
@@ -11,11 +13,25 @@ import math
 import torch
 
 
+def scheduled_lr(lr: float, t: int, warmup_steps: int, total_steps: int, end_lr: float) -> float:
+    """Learning rate of step t (1-based): linear warm-up from 0 to `lr` over `warmup_steps`,
+    polynomial decay (power 2) to `end_lr` at `total_steps`, `end_lr` after that.  The device
+    computes the same expression (opt_hparams_sched_kernel)."""
+    if t <= warmup_steps:
+        return lr * t / warmup_steps
+    if t < total_steps:
+        rem = (total_steps - t) / (total_steps - warmup_steps)
+        return end_lr + (lr - end_lr) * rem * rem
+    return end_lr
+
+
 class FlatOptimizer:
     """On the GPU the step counter and learning rate live in a device buffer
-    `hs = {t, lr, lr_t}` advanced by a one-thread kernel, so a captured step (HIP graph)
-    replays correctly; host-side changes (LR callbacks, checkpoint restore) are written to it
-    before the next step, outside any capture."""
+    `hs = {t, lr, lr_t, lr_sched, warmup_steps, total_steps, end_lr, -}` advanced by a
+    one-thread kernel, so a captured step (HIP graph) replays correctly; host-side changes (LR
+    callbacks, checkpoint restore) are written to it before the next step, outside any capture.
+    With a schedule (`set_schedule`) that kernel also derives the step's learning rate from the
+    step count, so a per-step schedule costs no host write at all."""
 
     def __init__(self, engine, lr: float):
         self.engine = engine
@@ -23,10 +39,11 @@ class FlatOptimizer:
         self.params = engine.params[: self.n]
         self.grads = engine.grads
         self.gscale = 1.0
-        self.hs = torch.zeros(4, dtype=torch.float32, device=self.params.device) if self.params.is_cuda else None
+        self.hs = torch.zeros(8, dtype=torch.float32, device=self.params.device) if self.params.is_cuda else None
         self._lr = float(lr)
         self._iterations = 0         # Keras `optimizer.iterations`
         self._dirty = True
+        self._sched = None           # (warmup_steps, total_steps, end_lr) or None
 
     @property
     def on_gpu(self):
@@ -50,17 +67,47 @@ class FlatOptimizer:
         self._iterations = int(v)
         self._dirty = True
 
+    def set_schedule(self, warmup_steps: int, total_steps: int, end_lr: float):
+        """Warm-up + polynomial decay of `lr` by step count (`scheduled_lr`), evaluated on the
+        device.  Install it before the step is captured into a graph: the capture records which
+        hparams kernel runs.  `lr` stays the peak rate; the position is `iterations`."""
+        warmup_steps, total_steps = int(warmup_steps), int(total_steps)
+        if warmup_steps < 0 or total_steps <= warmup_steps:
+            raise ValueError("schedule needs 0 <= warmup_steps < total_steps")
+        if total_steps >= 1 << 24:
+            raise ValueError("schedule: total_steps must stay below 2**24 (the device step counter is fp32)")
+        self._sched = (warmup_steps, total_steps, float(end_lr))
+        self._dirty = True
+
+    @property
+    def schedule(self):
+        return self._sched
+
+    def lr_at(self, t: int) -> float:
+        """The learning rate step t runs at (before Adam's bias correction)."""
+        return self._lr if self._sched is None else scheduled_lr(self._lr, t, *self._sched)
+
+    @property
+    def current_lr(self) -> float:
+        """The rate of the most recent step (the base rate before the first)."""
+        return self.lr_at(max(self._iterations, 1)) if self._sched is not None else self._lr
+
     def sync_hparams(self):
-        """Write host-side lr / step count into the device buffer (never inside a capture)."""
+        """Write host-side lr / step count / schedule into the device buffer (never inside a capture)."""
         if self.hs is not None and self._dirty:
-            self.hs.copy_(torch.tensor([float(self._iterations), self._lr, 0.0, 0.0]), non_blocking=False)
+            wu, tot, end = self._sched or (0, 0, 0.0)
+            self.hs.copy_(torch.tensor([float(self._iterations), self._lr, 0.0, 0.0, float(wu), float(tot), end, 0.0]),
+                          non_blocking=False)
             self._dirty = False
 
     def _device_step(self, adam: bool, b1=0.0, b2=0.0):
         from ..ops.native import native
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hparams()
-        native.opt_hparams(self.hs, b1, b2, adam)
+        if self._sched is None:
+            native.opt_hparams(self.hs, b1, b2, adam)
+        else:
+            native.opt_hparams_sched(self.hs, b1, b2, adam)
 
     def state_tensors(self):
         return {}
@@ -82,7 +129,7 @@ class Adam(FlatOptimizer):
         else:
             self._iterations += 1
             t = self._iterations
-            lr_t = self.lr * math.sqrt(1 - self.b2 ** t) / (1 - self.b1 ** t)
+            lr_t = self.lr_at(t) * math.sqrt(1 - self.b2 ** t) / (1 - self.b1 ** t)
             g = self.grads * self.gscale
             self.m.mul_(self.b1).add_(g, alpha=1 - self.b1)
             self.v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
@@ -106,10 +153,11 @@ class SGD(FlatOptimizer):
             native.sgd(self.params, self.grads, self.mom, 0.0, self.mu, self.wd, self.nesterov, self.gscale, self.hs)
         else:
             self._iterations += 1
+            lr = self.lr_at(self._iterations)
             g = self.grads * self.gscale + self.wd * self.params
-            self.mom.mul_(self.mu).sub_(self.lr * g)
+            self.mom.mul_(self.mu).sub_(lr * g)
             if self.nesterov:
-                self.params.add_(self.mu * self.mom - self.lr * g)
+                self.params.add_(self.mu * self.mom - lr * g)
             else:
                 self.params.add_(self.mom)
 
@@ -117,7 +165,105 @@ class SGD(FlatOptimizer):
         return {"momentum": self.mom}
 
 
+LARS_CHUNK = 16384       # floats per block of the norm / update passes (kLarsDefaultChunk)
+
+
+def lars_table(segments, chunk: int = LARS_CHUNK) -> torch.Tensor:
+    """Host segment table, int32 [nseg][4] = {offset, size, adapt, chunk0}, from (offset, size,
+    adapt) triples in ascending order.  chunk0 is the running count of ceil(size / chunk): block
+    chunk0 + c of both passes owns chunk c of the segment, so the table and the chunk size fix
+    the reduction order."""
+    rows, c0 = [], 0
+    for off, size, adapt in segments:
+        rows.append([int(off), int(size), int(bool(adapt)), c0])
+        c0 += -(-int(size) // chunk)
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
+
+
+def lars_chunks(table: torch.Tensor, chunk: int) -> int:
+    return int(sum(-(-int(size) // chunk) for size in table[:, 1].tolist()))
+
+
+def lars_segments(L):
+    """[(offset, size, adapt, layer name or None)] over the trainable prefix of a ParamLayout:
+    every `kernel` entry is one adapted segment (53 conv kernels + the dense kernel), runs of
+    per-channel entries (biases, BN gamma / beta) merge into non-adapted segments.  The
+    alignment padding after the last entry belongs to no segment."""
+    segs = []
+    ents = sorted((e for e in L.entries.values() if e.trainable), key=lambda e: e.offset)
+    for e in ents:
+        if e.kind == "kernel":
+            segs.append((e.offset, e.size, 1, e.layer))
+        elif segs and not segs[-1][2] and segs[-1][0] + segs[-1][1] == e.offset:
+            segs[-1] = (segs[-1][0], segs[-1][1] + e.size, 0, None)
+        else:
+            segs.append((e.offset, e.size, 0, None))
+    return segs
+
+
+class LARS(FlatOptimizer):
+    """Layer-wise adaptive rate scaling.  For a kernel w with gradient g (gs the gradient scale):
+        ratio = eta |w| / (|gs g| + wd |w| + eps)   (1 when either norm is 0)
+        v <- mu v + lr ratio (gs g + wd w);   w <- w - v
+    Biases and BN parameters take ratio 1 and no weight decay.  On the GPU the norms are a
+    segmented reduction in a fixed order (bit-identical on every replica and every run), and
+    lr, the step count and the trust ratios stay on the device, so the step captures into a
+    HIP graph."""
+
+    def __init__(self, engine, lr=0.1, momentum=0.9, weight_decay=0.0, eta=1e-3, eps=0.0, nesterov=False,
+                 chunk=None):
+        if nesterov:
+            raise ValueError("LARS has no Nesterov form here: use --optimizer sgd --nesterov, or drop --nesterov")
+        super().__init__(engine, lr)
+        self.mu, self.wd, self.eta, self.eps = momentum, weight_decay, eta, eps
+        self.nesterov = False
+        self.mom = torch.zeros_like(self.params)
+        self.chunk = int(chunk or LARS_CHUNK)
+        self.segments = lars_segments(engine.L)
+        self.table_host = lars_table([s[:3] for s in self.segments], self.chunk)
+        dev = self.params.device
+        self.ratios = torch.ones(len(self.segments), dtype=torch.float32, device=dev)
+        if self.on_gpu:
+            self.table = self.table_host.to(dev)
+            self.partials = torch.zeros(2 * lars_chunks(self.table_host, self.chunk), dtype=torch.float32, device=dev)
+
+    def step(self):
+        if self.on_gpu:
+            from ..ops.native import native
+            self._device_step(False)
+            self._iterations += 1
+            native.lars(self.params, self.grads, self.mom, self.table, self.table_host, self.chunk, self.partials,
+                        self.ratios, 0.0, self.mu, self.wd, self.eta, self.eps, self.gscale, self.hs)
+        else:
+            self._iterations += 1
+            lr = self.lr_at(self._iterations)
+            for i, (off, size, adapt, _) in enumerate(self.segments):
+                w = self.params[off:off + size]
+                g = self.grads[off:off + size] * self.gscale
+                v = self.mom[off:off + size]
+                ratio, wd = 1.0, 0.0
+                if adapt:
+                    wd = self.wd
+                    wn, gn = float((w * w).sum().sqrt()), float((g * g).sum().sqrt())
+                    if wn > 0 and gn > 0:
+                        ratio = self.eta * wn / (gn + wd * wn + self.eps)
+                self.ratios[i] = ratio
+                v.mul_(self.mu).add_(g + wd * w, alpha=lr * ratio)
+                w.sub_(v)
+
+    def state_tensors(self):
+        return {"momentum": self.mom}
+
+    def trust_ratios(self):
+        """{layer name: trust ratio of the most recent step} for the adapted (kernel) segments."""
+        r = self.ratios.detach().cpu().tolist()
+        return {name: r[i] for i, (_, _, adapt, name) in enumerate(self.segments) if adapt}
+
+
 def make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
+    if name == "lars":
+        return LARS(engine, lr, kw.get("momentum", 0.9), kw.get("weight_decay", 0.0), kw.get("lars_eta", 1e-3),
+                    kw.get("lars_eps", 0.0), kw.get("nesterov", False))
     if name == "adam":
         return Adam(engine, lr, kw.get("beta1", 0.9), kw.get("beta2", 0.999), kw.get("eps", 1e-7))
     if name == "sgd":

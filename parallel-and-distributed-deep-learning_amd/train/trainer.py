@@ -40,6 +40,8 @@ class Trainer:
         self.stop_training = False
         self.steps_per_epoch = None
         self.lr = cfg.lr * (strategy.num_replicas_in_sync if cfg.lr_scale_by_size else 1)
+        self.base_lr = self.lr       # --lr-schedule poly: the peak rate (self.lr then follows the schedule)
+        self.schedule = None         # (warmup_steps, total_steps, end_lr) once fit installs it
         strategy.setup(self)
         strategy.set_lr(self.lr)
 
@@ -51,6 +53,20 @@ class Trainer:
     def set_lr(self, lr: float):
         self.lr = float(lr)
         self.strategy.set_lr(self.lr)
+
+    def _install_schedule(self, epochs: int, spe: int):
+        """--lr-schedule poly: the optimizers evaluate the schedule on the device from their own
+        step count (restored by --resume), so nothing is written to the device per step; the
+        host evaluates the same formula only to report it."""
+        cfg = self.cfg
+        self.schedule = (cfg.warmup_epochs * spe, epochs * spe, cfg.lr_end)
+        self.strategy.set_schedule(*self.schedule)
+
+    def _scheduled_lr(self, fallback_step: int) -> float:
+        from .optim import scheduled_lr
+        opt = getattr(self.strategy, "opt", None)
+        t = opt.iterations if opt is not None else fallback_step
+        return scheduled_lr(self.base_lr, max(int(t), 1), *self.schedule)
 
     def sync(self):
         self.strategy.sync()
@@ -128,6 +144,8 @@ class Trainer:
         if cfg.max_steps:
             spe = min(spe, cfg.max_steps)
         self.steps_per_epoch = spe
+        if cfg.lr_schedule == "poly":
+            self._install_schedule(epochs, spe)
         vsteps = validation_steps or cfg.validation_steps
         if val_pipe is not None:
             vsteps = min(vsteps or val_pipe.num_batches(), val_pipe.num_batches() if not val_pipe.repeat else 10 ** 12)
@@ -179,6 +197,8 @@ class Trainer:
                 logs["val_loss"] = vt[0] / max(vt[3], 1)
                 logs["val_accuracy"] = vt[1] / max(vt[3], 1)
             logs = {k: float(v) for k, v in logs.items()}
+            if self.schedule is not None:         # the rate of the epoch's last step, for the line and the JSONL
+                self.lr = logs["lr"] = self._scheduled_lr((epoch + 1) * spe)
             dt = time.time() - t0
             for cb in cbs:
                 cb.on_epoch_end(epoch, logs)
@@ -203,10 +223,12 @@ def default_callbacks(cfg, strategy, extra: Optional[List[Callback]] = None) -> 
     if cfg.strategy in ("horovod", "multiworker", "mirrored"):
         cbs.append(BroadcastGlobalVariablesCallback(0))
         cbs.append(MetricAverageCallback())
-    cbs.append(ReduceLROnPlateau(monitor="val_loss", factor=cfg.reduce_lr_factor, patience=cfg.reduce_lr_patience,
-                                 min_lr=cfg.min_lr))
+    poly = cfg.lr_schedule == "poly"     # the device-side schedule owns the rate: no callback may move it
+    if not poly:
+        cbs.append(ReduceLROnPlateau(monitor="val_loss", factor=cfg.reduce_lr_factor,
+                                     patience=cfg.reduce_lr_patience, min_lr=cfg.min_lr))
     cbs.append(EarlyStopping(monitor="val_loss", min_delta=cfg.early_stop_min_delta, patience=cfg.early_stop_patience))
-    if cfg.warmup_epochs:
+    if cfg.warmup_epochs and not poly:
         size = strategy.num_replicas_in_sync
         cbs.append(LearningRateWarmupCallback(cfg.lr * (size if cfg.lr_scale_by_size else 1),
                                               warmup_epochs=cfg.warmup_epochs, size=size, verbose=1))

@@ -196,7 +196,7 @@ def save_keras_h5(path: str, engine, optimizer=None, cfg=None, progress: Optiona
         w = wnames if ln == "resnet50" else (["dense/kernel:0", "dense/bias:0"] if ln == "dense" else [])
         attrs.append((f"model_weights/{ln}", "weight_names", w))
     if optimizer is not None:
-        oname = "Adam" if type(optimizer).__name__ == "Adam" else "SGD"
+        oname = type(optimizer).__name__ if type(optimizer).__name__ in ("Adam", "LARS") else "SGD"
         train_vars = [wn for wn in wnames if L.entries[wn].trainable] + ["dense/kernel:0", "dense/bias:0"]
         onames = [f"{oname}/iter:0"]
         datasets.append((f"optimizer_weights/{oname}/iter:0", np.array(optimizer.iterations, dtype=np.int64)))
@@ -212,6 +212,8 @@ def save_keras_h5(path: str, engine, optimizer=None, cfg=None, progress: Optiona
         lr = float(getattr(optimizer, "lr", 1e-3))
         ocfg = ({"name": "Adam", "learning_rate": lr, "decay": 0.0, "beta_1": optimizer.b1, "beta_2": optimizer.b2,
                  "epsilon": optimizer.eps, "amsgrad": False} if oname == "Adam"
+                else {"name": "LARS", "learning_rate": lr, "momentum": optimizer.mu, "weight_decay": optimizer.wd,
+                      "eta": optimizer.eta, "epsilon": optimizer.eps} if oname == "LARS"
                 else {"name": "SGD", "learning_rate": lr, "decay": 0.0, "momentum": optimizer.mu,
                       "nesterov": optimizer.nesterov})
         attrs.append(("", "training_config", json.dumps({
