@@ -283,19 +283,34 @@ void wgrad(Tensor x, int64_t H, int64_t W, int64_t R, int64_t S, int64_t stride,
 // bits [.., CI/8] uint8, out [.., CI] bf16, colsum fp32 >= partial rows x CI, dw fp32 [CO][>=CI];
 // (CO, CI) = (256, 64) or (512, 128).
 void bwd1x1(Tensor g, Tensor x, Tensor wd, Tensor bits, Tensor out, Tensor colsum, Tensor dw, OptT out2, OptT g1,
-            OptT w1d, OptT gmask, OptT gx, OptT colsum_gx) {
+            OptT w1d, OptT gmask, OptT gx, OptT colsum_gx, OptT x2, OptT wd2, OptT out_s, OptT dw2) {
   pddl::Bwd1x1Params p{};
+  // dual form (a pre form that also runs the block's shortcut conv backward on the g tile):
+  // x2 [M,64] bf16, wd2 [64][>=256] bf16 rows, out_s [M,64] bf16, dw2 fp32 [256][>=64]; gx optional
+  const bool dual = x2.has_value() || wd2.has_value() || out_s.has_value() || dw2.has_value();
+  if (dual) {
+    PCHECK(x2.has_value() && wd2.has_value() && out_s.has_value() && dw2.has_value() && g1.has_value(),
+           "bwd1x1 dual form: x2, wd2, out_s, dw2 together with the pre form operands");
+    PCHECK(g.size(-1) == 256 && x.size(-1) == 64, "bwd1x1 dual form: (CO, CI) must be (256, 64)");
+    PCHECK(x2->is_contiguous() && x2->size(-1) == 64 && rows_of(*x2) == rows_of(g), "bwd1x1: x2 [M,64]");
+    PCHECK(out_s->is_contiguous() && out_s->size(-1) == 64 && rows_of(*out_s) == rows_of(g), "bwd1x1: out_s [M,64]");
+    PCHECK(wd2->dim() == 2 && wd2->size(0) == 64 && wd2->size(1) >= 256, "bwd1x1: wd2 must be [64][>=256]");
+    PCHECK(dw2->dim() == 2 && dw2->size(0) == 256 && dw2->size(1) >= 64, "bwd1x1: dw2 must be [256][>=64]");
+    p.x2 = bfp(*x2); p.wd2 = bfp(*wd2); p.ld_wd2 = ld(*wd2); p.out_s = bfpm(*out_s);
+    p.dw2 = f32p(*dw2); p.ld_dw2 = ld(*dw2);
+  }
   if (g1.has_value()) {   // pre form: g = bit(gmask) * (g1 . w1d^T + g) computed per tile, written to gx
-    PCHECK(!out2.has_value() && w1d.has_value() && gmask.has_value() && gx.has_value() && colsum_gx.has_value(),
+    PCHECK(!out2.has_value() && w1d.has_value() && gmask.has_value() && (gx.has_value() || dual) && colsum_gx.has_value(),
            "bwd1x1 pre form: g1, w1d, gmask, gx, colsum_gx together, stride-1 only");
     PCHECK(g.size(-1) == 256 && g1->size(-1) == 64 && g1->is_contiguous() && rows_of(*g1) == rows_of(g),
            "bwd1x1 pre form: g1 [M,64] next to g [M,256]");
     PCHECK(w1d->dim() == 2 && w1d->size(0) == 256 && w1d->size(1) == 64 && w1d->is_contiguous(), "bwd1x1: w1d [256,64]");
     PCHECK(gmask->scalar_type() == torch::kUInt8 && gmask->numel() == rows_of(g) * 32, "bwd1x1: gmask [M,32] uint8");
-    PCHECK(gx->sizes() == g.sizes() && gx->is_contiguous() && gx->scalar_type() == torch::kBFloat16, "bwd1x1: gx like g");
-    PCHECK(colsum_gx->numel() >= (int64_t)pddl::bwd1x1_partial_rows((int)rows_of(g), 256, 64) * 256,
+    if (gx.has_value())
+      PCHECK(gx->sizes() == g.sizes() && gx->is_contiguous() && gx->scalar_type() == torch::kBFloat16, "bwd1x1: gx like g");
+    PCHECK(colsum_gx->numel() >= (int64_t)pddl::bwd1x1_partial_rows((int)rows_of(g), 256, 64, dual) * 256,
            "bwd1x1: colsum_gx too small");
-    p.g1 = bfp(*g1); p.w1d = bfp(*w1d); p.gmask = gmask->data_ptr<uint8_t>(); p.gx = bfpm(*gx);
+    p.g1 = bfp(*g1); p.w1d = bfp(*w1d); p.gmask = gmask->data_ptr<uint8_t>(); p.gx = gx.has_value() ? bfpm(*gx) : nullptr;
     p.colsum_gx = f32p(*colsum_gx);
   }
   PCHECK(g.is_contiguous() && x.is_contiguous() && out.is_contiguous() && bits.is_contiguous(), "bwd1x1: contiguous operands");
@@ -317,15 +332,15 @@ void bwd1x1(Tensor g, Tensor x, Tensor wd, Tensor bits, Tensor out, Tensor colsu
   PCHECK(bits.is_cuda() && bits.scalar_type() == torch::kUInt8, "bwd1x1: bits must be a uint8 GPU tensor");
   PCHECK(wd.dim() == 2 && wd.size(0) == CI && wd.size(1) >= CO, "bwd1x1: wd must be [CI][>=CO]");
   PCHECK(dw.dim() == 2 && dw.size(0) == CO && dw.size(1) >= CI, "bwd1x1: dw must be [CO][>=CI]");
-  PCHECK(colsum.is_contiguous() && colsum.numel() >= (int64_t)pddl::bwd1x1_partial_rows((int)M, (int)CO, (int)CI) * CI,
+  PCHECK(colsum.is_contiguous() && colsum.numel() >= (int64_t)pddl::bwd1x1_partial_rows((int)M, (int)CO, (int)CI, dual) * CI,
          "bwd1x1: colsum too small");
   p.g = bfp(g); p.x = bfp(x); p.wd = bfp(wd); p.ld_wd = ld(wd); p.bits = bits.data_ptr<uint8_t>();
   p.out = bfpm(out); p.colsum = f32p(colsum); p.dw = f32p(dw); p.ld_dw = ld(dw);
   p.M = (int)M; p.CO = (int)CO; p.CI = (int)CI;
   ok(pddl::bwd1x1_launch(p, cur_stream()), "bwd1x1");
 }
-int64_t bwd1x1_partial_rows(int64_t M, int64_t CO, int64_t CI) {
-  return pddl::bwd1x1_partial_rows((int)M, (int)CO, (int)CI);
+int64_t bwd1x1_partial_rows(int64_t M, int64_t CO, int64_t CI, bool dual) {
+  return pddl::bwd1x1_partial_rows((int)M, (int)CO, (int)CI, dual);
 }
 
 // fp32 convolution (reference precision): y[N,Ho,Wo,Cout] = conv(x[N,H,W,C], w[Cout, R*S*C]) (+ bias)
@@ -893,8 +908,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bwd1x1", &bwd1x1, REL, py::arg("g"), py::arg("x"), py::arg("wd"), py::arg("bits"), py::arg("out"),
         py::arg("colsum"), py::arg("dw"), py::arg("out2") = py::none(), py::arg("g1") = py::none(),
         py::arg("w1d") = py::none(), py::arg("gmask") = py::none(), py::arg("gx") = py::none(),
-        py::arg("colsum_gx") = py::none());
-  m.def("bwd1x1_partial_rows", &bwd1x1_partial_rows);
+        py::arg("colsum_gx") = py::none(), py::arg("x2") = py::none(), py::arg("wd2") = py::none(),
+        py::arg("out_s") = py::none(), py::arg("dw2") = py::none());
+  m.def("bwd1x1_partial_rows", &bwd1x1_partial_rows, py::arg("M"), py::arg("CO"), py::arg("CI"), py::arg("dual") = false);
   m.def("conv_f32", &conv_f32, REL);
   m.def("conv_f32_epi", &conv_f32_epi, REL, py::arg("x"), py::arg("R"), py::arg("S"), py::arg("stride"),
         py::arg("pad"), py::arg("Ho"), py::arg("Wo"), py::arg("w"), py::arg("epi"), py::arg("scale") = none,

@@ -100,9 +100,17 @@ struct Bwd1x1Params {
   const uint8_t* gmask;                // [M][CO / 8] ReLU bits of this block's output
   uint16_t* gx;                        // [M][CO]
   float* colsum_gx;                    // [bwd1x1_partial_rows][CO]
+  // "dual" form (a pre form whose block has a shortcut conv on the same output gradient,
+  // conv2_block1): that conv's two GEMMs run on the g tile as well -- out_s = g . wd2 (no mask, no
+  // column sums), dw2 += g^T . x2 -- and gx may be null: g then never reaches HBM
+  const uint16_t* x2;                  // [M][64] the block input
+  const uint16_t* wd2; int ld_wd2;     // the shortcut's data-gradient weights [64][ld_wd2 >= 256]
+  uint16_t* out_s;                     // [M][64] the shortcut's data gradient
+  float* dw2; int ld_dw2;              // fp32 [256][ld_dw2 >= 64], accumulated with atomics
 };
 const char* bwd1x1_launch(const Bwd1x1Params& p, hipStream_t stream);
-int bwd1x1_partial_rows(int M, int CO, int CI);
+// (dual: the rows a dual-form launch writes -- one 8-wave workgroup per CU)
+int bwd1x1_partial_rows(int M, int CO, int CI, bool dual = false);
 
 // ---- fp32 convolution on the fp32 matrix cores (conv_f32.hip): the reference-precision path ----
 struct ConvF32Params {

@@ -59,6 +59,10 @@ class HipEngine:
     C64_MIN_M = 262144      # ... from 4 x 256 CUs x 256-pixel tiles up (b >= 84 at 56 x 56)
     C3C1_OK = True          # stage-2 boundaries: conv3 + next conv1 fused (c3c1.hip)
     S2C_OK = True           # blocks feeding a downsampling block store only their stride-2 grid
+    PROJ_BWD_OK = True      # conv2_block1: shortcut conv backward inside the fused conv3 backward
+    PROJ_BWD_MIN_M = 200704 # ... from b64 at 56 x 56 up: b32 measured a wash (3.620 -> 3.629 ms against a 0.014
+                            # spread, two streams: the shortcut's weight gradient leaves the side stream),
+                            # b64 -0.9 %, b128 -1.0 %, b256 -1.1 %, b2560 -1.7 % (profiles/proj_bwd_b2560.txt)
     TWO_STREAM_MAX_BATCH = 1024
     # Engines whose steps replay from HIP graphs run ONE stream (two_stream=1 forces the side
     # stream into their graphs).  The runtime launches a single-stream graph from pre-built
@@ -146,6 +150,11 @@ class HipEngine:
         # stage-2 backward boundaries: the next block's conv1 data gradient computed inside this
         # block's fused conv3 backward (bwd1x1 pre form), its 256-channel result never re-read
         self.c1pre = self.C3C1_OK and opt(E, "c1pre", True)
+        # conv2_block1 (the stage-2 projection block): its shortcut conv's data and weight gradient
+        # run on the same output-gradient tile inside that launch (bwd1x1 dual form), so the
+        # 256-channel gradient of the block's output never reaches HBM
+        self.proj_bwd = self.PROJ_BWD_OK and opt(E, "proj_bwd", True)
+        self.proj_bwd_min_m = opt(E, "proj_bwd_min_m", self.PROJ_BWD_MIN_M)
         # blocks whose output feeds a downsampling block (conv2_block3, conv3_block4, conv4_block6):
         # every consumer of that output (the next block's stride-2 conv1 and shortcut, forward and
         # weight gradient, and its ReLU mask) reads only the even rows / columns, so conv3 runs on
@@ -423,7 +432,7 @@ class HipEngine:
                 Hc = Ho // 2 + Ho % 2
                 Mc = B * Hc * Hc
             if self._bwd_fused(bi, b, s2) or self._bwd_fused_s2(bi, b, s2):     # fused c3 backward -> g2
-                add(b.convs["2"].name, N.bwd1x1_partial_rows(Mc, 4 * f, f), f)
+                add(b.convs["2"].name, N.bwd1x1_partial_rows(Mc, 4 * f, f, self._proj_bwd(bi, s2, B)), f)
             else:
                 add(b.convs["2"].name, N.igemm_partial_rows(Mc, f, 4 * f), f)     # c3 dgrad -> g2
             if self._use_c64(f, M, Ho, self.bitmask):                           # c2 dgrad -> g1
@@ -432,7 +441,8 @@ class HipEngine:
                 add(b.convs["1"].name, N.igemm_partial_rows(M, f, 9 * f), f)
             if bi > 0:                                                           # c1 dgrad -> g_out(prev)
                 if self._pre_fused(bi, s2):   # (computed inside block bi-1's fused conv3 backward)
-                    add(blocks[bi - 1].convs["3"].name, N.bwd1x1_partial_rows(M, 256, 64), b.cin)
+                    add(blocks[bi - 1].convs["3"].name, N.bwd1x1_partial_rows(M, 256, 64, self._proj_bwd(bi - 1, s2, B)),
+                        b.cin)
                 else:
                     add(blocks[bi - 1].convs["3"].name, N.igemm_partial_rows(M, b.cin, 5 * f if b.proj else f), b.cin)
         if self.fuse_stem:   # (fused pool backward + conv1 weight gradient: one partial row per workgroup)
@@ -490,6 +500,15 @@ class HipEngine:
         b, pb = L.blocks[bi], L.blocks[bi - 1]
         return (b.filters == 64 and pb.filters == 64 and not b.proj and b.stride == 1 and bi - 1 not in s2
                 and self._bwd_fused(bi - 1, pb, s2))
+
+    def _proj_bwd(self, bi, s2, B) -> bool:
+        """Block bi's shortcut conv backward runs inside its fused conv3 backward (bwd1x1 dual
+        form): a stride-1 64-filter projection block (conv2_block1) that receives the pre form, from
+        proj_bwd_min_m GEMM rows up."""
+        b = self.L.blocks[bi]
+        H, Ho = self.geo[b.name]
+        return bool(self.proj_bwd and b.proj and b.filters == 64 and b.stride == 1 and bi + 1 < len(self.L.blocks)
+                    and B * Ho * Ho >= self.proj_bwd_min_m and self._pre_fused(bi + 1, s2))
 
     def _bwd_fused(self, bi, b, s2):
         # stage 2 (256 <- 64 channels) and stage 3 (512 <- 128); PDDL_ENGINE fuse_bwd=2: stage 2 only
@@ -833,6 +852,7 @@ class HipEngine:
             g2_n = f"s2g2f{bi}" if bi in s2 else f"g2_{rk}"
             assert pre is None or self._bwd_fused(bi, b, s2)
             pre_next = None
+            gs = None    # the shortcut conv's data gradient, when the fused conv3 backward produced it
             if bi in s2:
                 # gout is zero off the stride-2 grid (the next block reads only even rows /
                 # columns); its compact copy `gc` came from that block's dgrad epilogue
@@ -851,7 +871,17 @@ class HipEngine:
             elif self._bwd_fused(bi, b, s2):
                 # conv3: data and weight gradient from one read of gout
                 self._before_write(g2_n)
-                if pre is not None:
+                if pre is not None and self._proj_bwd(bi, s2, B):
+                    # ... and of a projection block not even written: the shortcut conv's data
+                    # gradient (gs, unmasked: conv1's data gradient below adds it and applies the
+                    # block input's mask) and weight gradient come out of the same launch.  gs takes
+                    # the head of the slot gout would have had.
+                    gs = self.gbuf[cur][: B * Ho * Ho * cin].view(B, Ho, Ho, cin)
+                    N.bwd1x1(pre["add"], y2, self._wdv(c3n, f, 4 * f), y2m, g2, part(c2n), self._gview(c3n, 4 * f, f),
+                             g1=pre["g1"], w1d=pre["w1d"], gmask=pre["gmask"], gx=None, colsum_gx=pre["cs"],
+                             x2=x_in, wd2=self._wdv(c1n, cin, 5 * f)[:, f:], out_s=gs,
+                             dw2=self._gview(c1n, 5 * f, cin)[f:])
+                elif pre is not None:
                     # gout itself is computed per tile from the next block's conv1 gradient
                     # (pre form): this block's output gradient is written once, never re-read
                     N.bwd1x1(pre["add"], y2, self._wdv(c3n, f, 4 * f), y2m, g2, part(c2n), self._gview(c3n, 4 * f, f),
@@ -878,7 +908,19 @@ class HipEngine:
             nxt = (cur + 1) % len(self.gbuf)
             gx = self.gbuf[nxt][: B * H * H * cin].view(B, H, H, cin)
             gx_n = [f"gbuf{nxt}"]
-            if b.proj:
+            if b.proj and gs is not None:
+                # the shortcut conv's gradients came out of the fused conv3 backward: conv1 alone.
+                # (Two streams: its weight gradient no longer reads gout; the shortcut's was added
+                # by the compute stream before the event _side_run records for the finalize below,
+                # which the side stream waits for -- so the finalize follows both contributions.)
+                self._wgrad(x_in, g1, self._gview(c1n, 5 * f, cin)[:f], H, Ho, reads=(f"g1_{rk}",))
+                W(N.wgrad_finalize, self.params, self.grads, self._fin_tabs[b.name], 4, self.scale, self.dgr,
+                  self._fin_rows_n[b.name])
+                self._before_write(*gx_n)
+                self._igemm(g1, self._wdv(c1n, cin, 5 * f), gx, Ho, Ho, mode=IGEMM_DGRAD, mask=mask_in, add=gs,
+                            colsum=cs_in)
+                last = L.entry(b.convs["0"].name, "kernel")
+            elif b.proj:
                 Hx, sx = self._x_geom(bi, H, b.stride)
                 self._wgrad(x_in, g1, self._gview(c1n, 5 * f, cin), Hx, Ho, stride=sx, g2=gout, co_split=f,
                             reads=(f"g1_{rk}", gout_n))

@@ -44,6 +44,7 @@ class HipEngineBNTrain(HipEngine):
     C64_OK = False         # (train-mode BN needs the batch statistics from the conv epilogue)
     C3C1_OK = False
     S2C_OK = False
+    PROJ_BWD_OK = False
 
     def __init__(self, layout: ParamLayout, batch: int, **kw):
         kw.setdefault("bn_mode", "train")

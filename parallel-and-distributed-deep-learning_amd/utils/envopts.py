@@ -24,6 +24,8 @@ KEYS: Dict[str, Dict[str, str]] = {
         "c64_min_m": "GEMM rows from which the row-tile kernels run (default 262144)",
         "c3c1": "1: stage-2 block boundaries as conv3 + next conv1 in one launch",
         "c1pre": "1: next block's conv1 dgrad inside the fused conv3 backward (stage 2)",
+        "proj_bwd": "1: conv2_block1's shortcut conv backward inside its fused conv3 backward (needs c1pre)",
+        "proj_bwd_min_m": "GEMM rows from which it runs (default 200704: b64 at 224)",
         "s2c": "1: blocks feeding a downsampling block store only their stride-2 grid",
         "bitmask": "1: ReLU masks as 1-bit masks (0: re-read the bf16 activation)",
         "grad_ring": "gradient buffers per kind of the two-stream backward (default 16 at b <= 64, else 5)",

@@ -86,13 +86,21 @@ def schedule(B, crop, fuse=True, fuse_bwd=True, fuse_bwd3=True, fuse_s2=True, fu
     def pre_fused(i):   # engine._pre_fused: block i's conv1 dgrad inside block i-1's fused conv3 backward
         return (c1pre_on and i >= 1 and blocks[i].filters == 64 and blocks[i - 1].filters == 64 and not blocks[i].proj
                 and blocks[i].stride == 1 and fused_c3(i - 1))
+
+    def proj_bwd(i):    # engine._proj_bwd: block i's shortcut conv backward inside its fused conv3 backward
+        return (opt(E, "proj_bwd", True) and blocks[i].proj and blocks[i].filters == 64 and blocks[i].stride == 1
+                and i + 1 < len(blocks) and B * geo[i][2] ** 2 >= opt(E, "proj_bwd_min_m", 200704) and pre_fused(i + 1))
     for bi in range(len(geo) - 1, -1, -1):
         b, H, Ho = geo[bi]
         f, cin = b.filters, b.cin
         M = B * Ho * Ho
         # blocks feeding a stride-2 block: conv3 wgrad/dgrad and conv2 wgrad on the compact quarter
         Mc = B * (Ho // 2 + Ho % 2) ** 2 if bi in s2 else M
-        if bi + 1 < len(geo) and pre_fused(bi + 1):
+        if proj_bwd(bi):   # dual form: g is neither written nor re-read; reads g1, add, x, x2, writes out, out_s
+            ev.append(("bwd1x1", f"{blocks[bi + 1].name} c1 dgrad + {b.name} c3+c0 dgrad+wgrad",
+                       4 * M * f * 4 * f + 2 * M * 4 * f * f + 4 * M * cin * 4 * f,
+                       (M * f + M * 4 * f + 2 * M * f + 2 * M * cin) * 2))
+        elif bi + 1 < len(geo) and pre_fused(bi + 1):
             ev.append(("bwd1x1", f"{blocks[bi + 1].name} c1 dgrad + {b.name} c3 dgrad+wgrad",
                        4 * Mc * f * 4 * f + 2 * M * 4 * f * f, (M * f + 3 * M * 4 * f + 2 * Mc * f) * 2))
         elif fuse_bwd and (f == 64 or (f == 128 and fuse_bwd3)) and (bi not in s2 or fuse_s2):   # bwd1x1: one read of g
@@ -107,13 +115,18 @@ def schedule(B, crop, fuse=True, fuse_bwd=True, fuse_bwd3=True, fuse_s2=True, fu
         ev.append(("conv3x3c64" if c64 else "igemm", f"{b.name} c2 dgrad", 2 * M * 9 * f * f, 3 * M * f * 2,
                    (M, f, 9 * f)))
         n1 = 5 * f if b.proj else f
-        if b.proj:   # conv1 and the shortcut conv: one wgrad launch per gradient source
+        if proj_bwd(bi):   # (the shortcut conv's weight gradient came out of the fused conv3 backward)
+            ev.append(("wgrad", f"{b.name} c1 wgrad", 2 * M * cin * f, (M * f + B * H * H * cin) * 2))
+        elif b.proj:   # conv1 and the shortcut conv: one wgrad launch per gradient source
             ev.append(("wgrad", f"{b.name} c1 wgrad", 2 * M * cin * f, (M * f + B * H * H * cin) * 2))
             ev.append(("wgrad", f"{b.name} c0 wgrad", 2 * M * cin * 4 * f, (M * 4 * f + B * H * H * cin) * 2))
         else:
             ev.append(("wgrad", f"{b.name} c1 wgrad", 2 * M * cin * n1, (M * n1 + B * H * H * cin) * 2))
         ev.append(("wgrad_finalize", b.name, 0, 0))
         if pre_fused(bi):
+            continue
+        if proj_bwd(bi):   # conv1 alone, the shortcut's data gradient added in the epilogue
+            ev.append(("igemm", f"{b.name} c1 dgrad", 2 * M * cin * f, (M * f + 2 * M * cin) * 2, (M, cin, f)))
             continue
         ev.append(("igemm", f"{b.name} c1 dgrad", 2 * M * cin * n1, (M * n1 + 3 * B * H * H * cin) * 2, (M, cin, n1),
                    "dual" if b.proj else ""))
