@@ -21,55 +21,17 @@ import torch.nn.functional as F
 from pddl.models.engine import _BNG_FMT, _FIN_FMT, _FUSE_FMT, _PREP_FMT, IGEMM_DGRAD, STEM_K
 from pddl.models.resnet50 import BN_EPS
 
+from kernel_checks import SENT16, SENT32, U, bits, dev, is_sent, rel64, sent, table, ulps
+
 pytestmark = pytest.mark.gpu
 
-dev = "cuda"
-SENT16 = 0x7FA5          # bf16 sentinel: a NaN no kernel here produces
-SENT32 = 0x7FA5A5A5      # fp32 sentinel
 EPS = float(torch.tensor(BN_EPS, dtype=torch.float32))   # the value the kernels receive
-U = 2.0 ** -24           # fp32 unit round-off
 ULP1_SHARE = 1e-3        # cap on the share of bf16 elements off by exactly one ulp
 
 
 def N():
     from pddl.ops.native import require_native
     return require_native()
-
-
-# ----------------------------------------------------------------------------- helpers
-def sent(n, dtype):
-    if dtype == torch.bfloat16:
-        return torch.full((n,), SENT16, dtype=torch.int16, device=dev).view(torch.bfloat16)
-    return torch.full((n,), SENT32, dtype=torch.int32, device=dev).view(torch.float32)
-
-
-def bits(t):
-    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def is_sent(t):
-    return bits(t) == (SENT16 if t.element_size() == 2 else SENT32)
-
-
-def okey(t):
-    """Bit pattern -> integer that orders like the value: differences are distances in ulps."""
-    if t.element_size() == 2:
-        b = t.view(torch.int16).to(torch.int32)
-        return torch.where(b < 0, -(b & 0x7FFF), b)
-    b = t.view(torch.int32).to(torch.int64)
-    return torch.where(b < 0, -(b & 0x7FFFFFFF), b)
-
-
-def ulps(got, want):
-    return (okey(got.contiguous()) - okey(want.contiguous())).abs()
-
-
-def rel64(got, ref):
-    return ((got.double() - ref).norm() / (ref.norm() + 1e-300)).item()
-
-
-def table(rows):
-    return torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8).clone().to(dev)
 
 
 class Alloc:
