@@ -801,6 +801,17 @@ void lars(Tensor p, Tensor g, Tensor mom, Tensor table, Tensor table_host, int64
 }
 void scale_(Tensor x, double a) { ok(pddl::scale_launch(f32p(x), x.numel(), (float)a, cur_stream()), "scale"); }
 void cast_bf16(Tensor x, Tensor y) { ok(pddl::cast_bf16_launch(f32p(x), bfpm(y), x.numel(), cur_stream()), "cast"); }
+void grad_accum(Tensor acc, Tensor g, int64_t mode) {
+  PCHECK(acc.is_contiguous() && g.is_contiguous() && acc.numel() == g.numel() && acc.device() == g.device(),
+         "grad_accum: acc and g contiguous, of one length, on one device");
+  PCHECK(mode >= 0 && mode <= 2, "grad_accum: mode is 0 (store), 1 (add) or 2 (fold)");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(g.device());
+  ok(pddl::grad_accum_launch(f32p(acc), f32p(g), g.numel(), (int)mode, cur_stream()), "grad_accum");
+}
+int64_t grad_accum_sweep(int64_t device) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard((int)device);
+  return pddl::grad_accum_sweep();
+}
 void cast_f32(Tensor x, Tensor y) { ok(pddl::cast_f32_launch(bfp(x), f32p(y), x.numel(), cur_stream()), "cast"); }
 
 }  // namespace
@@ -1029,6 +1040,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scale_", &scale_, REL);
   m.def("cast_bf16", &cast_bf16, REL);
   m.def("cast_f32", &cast_f32, REL);
+  m.def("grad_accum", &grad_accum, REL, py::arg("acc"), py::arg("g"), py::arg("mode"));
+  m.def("grad_accum_sweep", &grad_accum_sweep, REL);
   m.attr("PREP_LAYER_BYTES") = (int)sizeof(pddl::PrepLayer);
   m.attr("FUSE_LAYER_BYTES") = (int)sizeof(pddl::FuseLayer);
   m.attr("FIN_LAYER_BYTES") = (int)sizeof(pddl::FinLayer);

@@ -392,6 +392,10 @@ const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSe
 const char* adam_bf16_wire_launch(float* p, const uint16_t* g, float* m, float* v, uint16_t* snap, long n, float lr_t,
                                   float b1, float b2, float eps, hipStream_t s);
 const char* scale_launch(float* x, long n, float a, hipStream_t s);
+// Gradient accumulation over micro-batches: mode 0 acc = g (bitwise), 1 acc += g, 2 g += acc.  Any
+// float-aligned slices; n = 0 is a no-op.  grad_accum_sweep: floats per full grid sweep.
+const char* grad_accum_launch(float* acc, float* g, long n, int mode, hipStream_t s);
+long grad_accum_sweep();
 const char* cast_bf16_launch(const float* x, uint16_t* y, long n, hipStream_t s);
 const char* cast_f32_launch(const uint16_t* x, float* y, long n, hipStream_t s);
 

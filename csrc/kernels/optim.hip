@@ -235,6 +235,54 @@ __global__ void cast_f32_kernel(const uint16_t* __restrict__ x, float* __restric
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = bf2f(x[i]);
 }
 
+// Gradient accumulation over k micro-batches (train/accum.py).  mode 0 store: acc = g (bitwise);
+// 1 add: acc += g; 2 fold: g += acc, in place, so the all-reduce and the optimizers keep reading
+// the gradient buffer.  A pure streaming pass: 16 bytes per lane, two float4 per operand in
+// flight per lane, a grid-stride loop over a grid sized from the CU count.  Bucket slices start
+// at any float offset: block 0 peels a scalar head up to acc's next 16-byte boundary and the
+// scalar tail; vec = 0 (acc and g misaligned against each other) takes every element scalar.
+constexpr int kAccumBlock = 256, kAccumBlocksPerCu = 8, kAccumUnroll = 2;
+
+// dst = src (ADD = 0) or dst += src; fold is add with the operands swapped.
+template <int ADD>
+__device__ __forceinline__ void grad_accum_body(float* __restrict__ dst, const float* __restrict__ src, long n,
+                                                int vec) {
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+  if (!vec) {
+    for (long i = tid; i < n; i += nth) dst[i] = ADD ? dst[i] + src[i] : src[i];
+    return;
+  }
+  const long head = lmin((long)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) >> 2, n);
+  const long n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
+  if (blockIdx.x == 0) {   // at most 3 + 3 scalars: lanes 0..2 the head, lanes 64..66 the tail
+    long k = -1;
+    if ((long)threadIdx.x < head) k = threadIdx.x;
+    else if (threadIdx.x >= 64 && tail0 + (threadIdx.x - 64) < n) k = tail0 + (threadIdx.x - 64);
+    if (k >= 0) dst[k] = ADD ? dst[k] + src[k] : src[k];
+  }
+  v4f* d4 = reinterpret_cast<v4f*>(dst + head);
+  const v4f* s4 = reinterpret_cast<const v4f*>(src + head);
+  long i = tid;
+  for (; i + nth < n4; i += 2 * nth) {   // both lines' loads issue before the first store
+    const long j = i + nth;
+    const v4f x0 = s4[i], x1 = s4[j];
+    if (ADD) {
+      const v4f y0 = d4[i], y1 = d4[j];
+      d4[i] = y0 + x0;
+      d4[j] = y1 + x1;
+    } else {
+      d4[i] = x0;
+      d4[j] = x1;
+    }
+  }
+  if (i < n4) d4[i] = ADD ? d4[i] + s4[i] : s4[i];
+}
+__global__ __launch_bounds__(kAccumBlock) void grad_accum_kernel(float* acc, float* g, long n, int mode, int vec) {
+  if (mode == 0) grad_accum_body<0>(acc, g, n, vec);
+  else if (mode == 1) grad_accum_body<1>(acc, g, n, vec);
+  else grad_accum_body<1>(g, acc, n, vec);
+}
+
 static int grid_of(long n) { return (int)lmin((n + 255) / 256, 4096); }
 #define LAUNCH_RET                                        \
   {                                                       \
@@ -302,6 +350,22 @@ const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSe
 }
 const char* scale_launch(float* x, long n, float a, hipStream_t s) {
   hipLaunchKernelGGL(scale_kernel, dim3(grid_of(n)), dim3(256), 0, s, x, n, a);
+  LAUNCH_RET
+}
+// Floats one full sweep of the accumulation grid covers on the current device (tests pick
+// lengths around it).
+long grad_accum_sweep() { return (long)num_cus() * kAccumBlocksPerCu * kAccumBlock * 4 * kAccumUnroll; }
+const char* grad_accum_launch(float* acc, float* g, long n, int mode, hipStream_t s) {
+  if (mode < 0 || mode > 2) return "grad_accum: mode is 0 (store), 1 (add) or 2 (fold)";
+  if (n < 0) return "grad_accum: negative length";
+  if (n == 0) return nullptr;
+  if ((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 3) return "grad_accum: pointers are not float-aligned";
+  if (acc < g + n && g < acc + n) return "grad_accum: acc and g overlap";
+  // (slices at one offset of equally aligned buffers share their misalignment; anything else goes scalar)
+  const int vec = ((reinterpret_cast<uintptr_t>(acc) ^ reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+  const long per_block = (long)kAccumBlock * (vec ? 4 : 1);
+  const long grid = lmin((n + per_block - 1) / per_block, (long)num_cus() * kAccumBlocksPerCu);
+  hipLaunchKernelGGL(grad_accum_kernel, dim3((unsigned)grid), dim3(kAccumBlock), 0, s, acc, g, n, mode, vec);
   LAUNCH_RET
 }
 const char* adam_bf16_wire_launch(float* p, const uint16_t* g, float* m, float* v, uint16_t* snap, long n, float lr_t,

@@ -11,7 +11,7 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import config_from_args
+from .config import check_accum, config_from_args
 
 
 def _banner(cfg, strategy):
@@ -19,6 +19,7 @@ def _banner(cfg, strategy):
     print(f"Using pddl {__import__('pddl').__version__} (torch {torch.__version__}, HIP {torch.version.hip}), "
           f"strategy={cfg.strategy}, replicas={strategy.num_replicas_in_sync}, "
           f"per-replica batch={strategy.per_replica_batch}, global batch={strategy.global_batch}, "
+          f"accum_steps={cfg.accum_steps}, effective global batch={strategy.global_batch * cfg.accum_steps}, "
           f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}", flush=True)
 
 
@@ -54,8 +55,17 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
             sys.stderr.write(f"{what} is not supported for --strategy ps: the parameter servers apply Adam at a "
                              "host-set rate (use the mirrored, multiworker or horovod script for large batches)\n")
             return 2
+        if cfg.accum_steps != 1:
+            sys.stderr.write("--accum-steps is not supported for --strategy ps: every worker push is one asynchronous "
+                             "update on the parameter servers (use the single, mirrored, multiworker or horovod script)\n")
+            return 2
         from .parallel.parameter_server import run_ps_job
         return run_ps_job(cfg)
+    try:
+        check_accum(cfg)
+    except ValueError as e:
+        sys.stderr.write(f"{e}\n")
+        return 2
     if cfg.roctx:
         from .utils import profiling
         profiling.enable(True)

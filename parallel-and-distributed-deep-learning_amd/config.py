@@ -64,6 +64,7 @@ class TrainConfig:
     strategy: str = "single"                       # single | mirrored | multiworker | horovod | ps
     bucket_mb: float = 32.0                        # gradient bucket size (7-link xGMI tuned); <= 0: autotune
     grad_dtype: str = "fp32"                       # all-reduce dtype
+    accum_steps: int = 1                           # micro-batches per update (Horovod's backward_passes_per_step)
     num_ps: int = 1
     num_workers: int = 1
     port_base: int = 12345                         # SlurmClusterResolver(port_base=12345) (multiworkers.py:16)
@@ -125,6 +126,25 @@ PRESETS = {
 }
 
 
+def check_accum(cfg: TrainConfig) -> None:
+    """--accum-steps K: what cannot be combined with K > 1 is a configuration error, raised
+    before anything is built."""
+    k = cfg.accum_steps
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+        raise ValueError(f"--accum-steps must be an integer >= 1 (got {k!r})")
+    if k == 1:
+        return
+    if cfg.graphs is True:
+        raise ValueError("--graphs cannot be combined with --accum-steps > 1: the whole-step graph contains the "
+                         "optimizer update (drop --graphs; accumulation runs the eager step)")
+    if cfg.bucket_mb <= 0:
+        raise ValueError("--bucket-mb 0 (autotune) cannot be combined with --accum-steps > 1: the autotune times "
+                         "single steps (pass a bucket size)")
+    if cfg.strategy == "ps":
+        raise ValueError("--accum-steps > 1 is not supported for --strategy ps: every worker push is one "
+                         "asynchronous update on the parameter servers")
+
+
 def make_config(preset: str = "single", **overrides) -> TrainConfig:
     if preset not in PRESETS:
         raise ValueError(f"unknown preset {preset!r}; choose from {sorted(PRESETS)}")
@@ -165,6 +185,9 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="score the validation split (loss, top-1, top-5) with --weights / --resume loaded; trains and saves nothing")
     a("--bucket-mb", type=float, dest="bucket_mb")
     a("--grad-dtype", choices=["fp32", "bf16"], dest="grad_dtype")
+    a("--accum-steps", "--backward-passes-per-step", type=int, dest="accum_steps",
+      help="gradient accumulation: every K-th step all-reduces and applies ONE update from the mean gradient over "
+           "K micro-batches (effective global batch = K x global batch); --steps-per-epoch must be a multiple of K")
     a("--weights", type=str)
     a("--device", choices=["auto", "cpu", "cuda"])
     a("--seed", type=int)

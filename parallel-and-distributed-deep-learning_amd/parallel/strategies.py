@@ -120,7 +120,10 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
+        from ..config import check_accum
+        check_accum(cfg)
         self.cfg = cfg
+        self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
         self.rank = 0
         self.world = 1
         self.local_replicas = 1
@@ -197,6 +200,13 @@ class Strategy:
     def _replicas(self):
         return [(self.engine, self.opt)]
 
+    def _make_accum(self, engine, buckets=None):
+        """--accum-steps K > 1: the running gradient sum of `engine` (K = 1: nothing is allocated)."""
+        if self.cfg.accum_steps <= 1:
+            return None
+        from ..train.accum import GradAccumulator
+        return GradAccumulator(engine, self.cfg.accum_steps, buckets)
+
     # ------------------------------------------------------------------ data
     def _pipe(self, split: str, batch: int, shards: int, index: int) -> Pipeline:
         cfg = self.cfg
@@ -262,6 +272,7 @@ class SingleStrategy(Strategy):
         cap = max(self.cfg.batch_size, self.cfg.val_batch_size or 0)
         self.engine, self.opt = self._make_engine_and_opt(self.device, cap)
         self.aug = Augment(self.cfg, self.device, self.cfg.seed)
+        self.accum = self._make_accum(self.engine)
         self.graphed = None
         if self.cfg.graphs and self.device.type == "cuda" and hasattr(self.engine, "wbf"):
             from ..train.graph import GraphedTrainStep   # HIP-graph replay of the whole step
@@ -277,7 +288,14 @@ class SingleStrategy(Strategy):
             return self.graphed(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
                                 flip, off).clone()
         eng = self.engine
-        s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off).clone()
+        acc = self.accum
+        if acc is None:
+            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off).clone()
+        else:            # a micro-step: the update runs on every K-th call, from the mean over K batches
+            s = eng.forward_backward(images, labels, 1.0 / (B * acc.k), flip=flip, crop_offset=off).clone()
+            acc.accumulate()
+            if not acc.advance():
+                return s
         self.opt.step()
         eng.after_update()
         return s
@@ -323,6 +341,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
     def __init__(self, cfg, comm: str = "fusion"):
         super().__init__(cfg)
         self.comm = comm
+        self._update_due = True
 
     # (Round 6 removed the graphed-rank variant -- the step replayed from bucket-segmented HIP
     # graphs with each bucket all-reduced on a native RCCL communicator between the segment
@@ -355,6 +374,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
             self.fusion.shutdown()
         self.bucket_mb = bucket_mb
         self.buckets = self.engine.L.buckets(bucket_mb)
+        self.accum = self._make_accum(self.engine, self.buckets)
         self.fusion = None
         self.reducer = None
         if self.world > 1:
@@ -428,6 +448,8 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
             return g(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
                      flip, off).clone()
         s = self.compute_gradients(images, labels)
+        if not self._update_due:       # (--accum-steps: micro-steps 1..K-1 only accumulate)
+            return s
         prof.push("step/optimizer")
         self.opt.step()
         self.engine.after_update()
@@ -438,22 +460,37 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
         """Forward + backward + the bucketed all-reduce, without applying the update
         (Optimizer.compute_gradients of the reference's DistributedOptimizer,
         imagenet-resnet50-hvd.py:101): afterwards `engine.grads` holds the global-batch mean
-        gradient on every rank.  Returns the step's (loss sum, correct) stats."""
+        gradient on every rank.  Returns the step's (loss sum, correct) stats.  With
+        --accum-steps K every call is a micro-step: calls 1..K-1 accumulate locally and only the
+        K-th all-reduces (each bucket folded into the running sum before it is reported ready),
+        after which `engine.grads` holds the mean over the K global batches."""
         if getattr(self, "mirror", None) is not None:
             return self.mirror.compute_gradients(images, labels, self.global_batch)
         B = images.shape[0]
         flip, off = self.aug(B)
-        gscale = 1.0 / (B * self.world)
+        acc = self.accum
+        last = self._update_due = acc is None or acc.last
+        gscale = 1.0 / (B * self.world * (acc.k if acc is not None else 1))
         cb = None
         bks = self.buckets
         if self.fusion is not None:
-            self.fusion.begin_step()
+            if last:
+                self.fusion.begin_step()
             cb = self.fusion.bucket_ready
         elif self.reducer is not None:
-            self.reducer.begin()
+            if last:
+                self.reducer.begin()
             cb = self.reducer.on_bucket_ready
+        if acc is not None and cb is not None:
+            cb = acc.wrap(cb)
         s = self.engine.forward_backward(images, labels, gscale, flip=flip, crop_offset=off, bucket_cb=cb,
                                          buckets=bks).clone()
+        if acc is not None:
+            if cb is None:
+                acc.accumulate()
+            acc.advance()
+        if not last:
+            return s
         prof.push("step/allreduce")
         if self.fusion is not None:
             self.fusion.finish()
@@ -578,7 +615,9 @@ class _LocalReplicas:
         # (several replicas / ranks replay graphed segments unless --no-graphs; one replica in the
         # whole job runs eager unless --graphs)
         single = self._single_replica_job()
-        graphed = cfg.graphs is True or (cfg.graphs is None and not single)
+        self.accum_k = cfg.accum_steps
+        # (--accum-steps K > 1 runs eager: the segmented graphs bake one step's collectives into the replay)
+        graphed = cfg.graphs is True or (cfg.graphs is None and not single and self.accum_k == 1)
         # (segmented replica graphs defer their weight gradients into side graphs; a one-replica
         # job's --graphs whole-step graph stays one stream: GraphedTrainStep captures no side graphs)
         graphed = ("segmented" if not single else True) if graphed else False
@@ -620,6 +659,13 @@ class _LocalReplicas:
         # graph launch stream per replica (None: train/graph.py replay_stream of its device; the
         # host-loop rehearsal with every replica on one device gives each its own)
         self.launch_streams = None
+        self.accums = None           # one GradAccumulator per replica (K > 1), made with the first step's buckets
+
+    def _accums(self):
+        if self.accum_k > 1 and self.accums is None:
+            from ..train.accum import GradAccumulator
+            self.accums = [GradAccumulator(e, self.accum_k, self.buckets) for e, _ in self.replicas]
+        return self.accums
 
     # ------------------------------------------------------------------ state
     def broadcast(self):
@@ -950,6 +996,12 @@ class _LocalReplicas:
         if overlap:
             if not hasattr(self, "_q"):
                 self._overlap_setup()
+        # --accum-steps K: micro-steps 1..K-1 accumulate per replica and skip the reduction and the
+        # update; the K-th folds the running sum into each bucket before it is reported ready
+        accs = self._accums()
+        last = accs is None or accs[0].last
+        gscale = 1.0 / (global_batch * self.accum_k)
+        if overlap and last:
             nb = len(self.buckets)
             self._events = [[None] * R for _ in range(nb)]
             self._count = [0] * nb
@@ -963,8 +1015,15 @@ class _LocalReplicas:
                 torch.cuda.set_device(d)
             im, lb = parts[i]
             flip, off = self.augs[i](im.shape[0])
-            kw = dict(bucket_cb=self._bucket_cb(i), buckets=self.buckets) if overlap else {}
-            stats[i] = eng.forward_backward(im, lb, 1.0 / global_batch, flip=flip, crop_offset=off, **kw).clone()
+            kw = {}
+            if overlap:
+                cb = self._bucket_cb(i)
+                kw = dict(bucket_cb=accs[i].wrap(cb) if accs is not None else cb, buckets=self.buckets)
+            stats[i] = eng.forward_backward(im, lb, gscale, flip=flip, crop_offset=off, **kw).clone()
+            if accs is not None:
+                if not overlap:
+                    accs[i].accumulate()
+                accs[i].advance()
 
         if self.gpu and R > 1:
             th = [threading.Thread(target=run, args=(i,)) for i in range(R)]
@@ -975,6 +1034,8 @@ class _LocalReplicas:
         else:
             for i in range(R):
                 run(i)
+        if not last:
+            return self._sum_stats(stats)
         grads = [e.grads for e, _ in self.replicas]
         if overlap:
             comm_th.join()
@@ -1013,7 +1074,7 @@ class _LocalReplicas:
             if self.cfg.graphs:            # (--graphs: the whole step as one HIP graph)
                 return self._whole_step(parts, global_batch)
             return self._single_step(parts, global_batch)
-        if self.graph_mode:
+        if self.graph_mode and self.accum_k == 1:
             return self._graphed_step(parts, global_batch)
         return self._eager_step(parts, global_batch)
 
@@ -1032,7 +1093,12 @@ class _LocalReplicas:
         im, lb = parts[0]
         with torch.cuda.device(d):
             flip, off = self.augs[0](im.shape[0])
-            s = eng.forward_backward(im, lb, 1.0 / global_batch, flip=flip, crop_offset=off).clone()
+            accs = self._accums()
+            s = eng.forward_backward(im, lb, 1.0 / (global_batch * self.accum_k), flip=flip, crop_offset=off).clone()
+            if accs is not None:
+                accs[0].accumulate()
+                if not accs[0].advance():
+                    return s
             opt.step()
             eng.after_update()
         return s

@@ -225,6 +225,9 @@ class JsonlLogger(Callback):
         rec = {"epoch": epoch + 1, **{k: float(v) for k, v in (logs or {}).items()}}
         n = self.trainer.strategy.num_replicas_in_sync
         rec["replicas"] = n
+        k = getattr(self.trainer.cfg, "accum_steps", 1)
+        rec["accum_steps"] = k
+        rec["effective_global_batch"] = self.trainer.strategy.global_batch * k
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)

@@ -144,8 +144,13 @@ class Trainer:
         if cfg.max_steps:
             spe = min(spe, cfg.max_steps)
         self.steps_per_epoch = spe
+        K = cfg.accum_steps
+        if spe % K:
+            # (an epoch then never ends mid-accumulation: validation, checkpoints and --resume need no new state)
+            raise ValueError(f"steps per epoch ({spe}, after --max-steps) must be a multiple of --accum-steps ({K}): "
+                             "pass --steps-per-epoch / --max-steps as a multiple of it")
         if cfg.lr_schedule == "poly":
-            self._install_schedule(epochs, spe)
+            self._install_schedule(epochs, spe // K)      # the schedule counts updates, not micro-steps
         vsteps = validation_steps or cfg.validation_steps
         if val_pipe is not None:
             vsteps = min(vsteps or val_pipe.num_batches(), val_pipe.num_batches() if not val_pipe.repeat else 10 ** 12)
@@ -198,7 +203,7 @@ class Trainer:
                 logs["val_accuracy"] = vt[1] / max(vt[3], 1)
             logs = {k: float(v) for k, v in logs.items()}
             if self.schedule is not None:         # the rate of the epoch's last step, for the line and the JSONL
-                self.lr = logs["lr"] = self._scheduled_lr((epoch + 1) * spe)
+                self.lr = logs["lr"] = self._scheduled_lr((epoch + 1) * spe // K)
             dt = time.time() - t0
             for cb in cbs:
                 cb.on_epoch_end(epoch, logs)
