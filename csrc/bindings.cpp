@@ -458,11 +458,12 @@ void colsum_f32(Tensor g, int64_t C, Tensor out) {
   ok(pddl::colsum_f32_launch(f32p(g), g.numel() / ld(g), (int)C, ld(g), f32p(out), cur_stream()), "colsum_f32");
 }
 void softmax_xent_f32(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
-                      Tensor correct) {
+                      Tensor correct, double smoothing) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
+  PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "softmax_xent_f32: smoothing must be in [0, 1]");
   ok(pddl::softmax_xent_f32_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
                                    (int)ncls, (float)gscale, f32p(dlogits), ld(dlogits), f32p(loss_sum),
-                                   f32p(correct), cur_stream()),
+                                   f32p(correct), cur_stream(), (float)smoothing),
      "softmax_xent_f32");
 }
 void prep_f32(Tensor params, Tensor table, int64_t nlayers, Tensor wf32, Tensor scale, Tensor shift, double eps) {
@@ -682,20 +683,22 @@ void colsum_reduce(Tensor part, Tensor table, int64_t nlayers, Tensor colsum) {
      "colsum_reduce");
 }
 void softmax_xent(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
-                  Tensor correct) {
+                  Tensor correct, double smoothing) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
+  PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "softmax_xent: smoothing must be in [0, 1]");
   ok(pddl::softmax_xent_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
                                (int)ncls, (float)gscale, bfpm(dlogits), ld(dlogits), f32p(loss_sum),
-                               f32p(correct), cur_stream()),
+                               f32p(correct), cur_stream(), (float)smoothing),
      "softmax_xent");
 }
-void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out) {
+void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out, double smoothing) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda() && labels.is_contiguous(), "labels int64 GPU");
   PCHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && ncls <= logits.size(1),
          "eval_metrics: logits [B][>= ncls], labels [B]");
   PCHECK(out.numel() == 3 && out.is_contiguous(), "eval_metrics: out is 3 contiguous floats");
+  PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "eval_metrics: smoothing must be in [0, 1]");
   ok(pddl::eval_metrics_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0), (int)ncls,
-                               (int)k, f32p(out), cur_stream()),
+                               (int)k, f32p(out), cur_stream(), (float)smoothing),
      "eval_metrics");
 }
 void prep(Tensor params, Tensor table, int64_t nlayers, int64_t max_elems, Tensor wbf, Tensor scale, Tensor shift,
@@ -932,7 +935,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gap_fwd_f32", &gap_fwd_f32, REL);
   m.def("gap_bwd_f32", &gap_bwd_f32, REL);
   m.def("colsum_f32", &colsum_f32, REL);
-  m.def("softmax_xent_f32", &softmax_xent_f32, REL);
+  m.def("softmax_xent_f32", &softmax_xent_f32, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"),
+        py::arg("gscale"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0);
   m.def("prep_f32", &prep_f32, REL);
   m.def("wgrad_f32", &wgrad_f32, REL);
   m.def("stem_s2d", &stem_s2d, REL);
@@ -956,8 +960,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gap_fwd", &gap_fwd, REL);
   m.def("gap_bwd", &gap_bwd, REL);
   m.def("colsum", &colsum, REL);
-  m.def("softmax_xent", &softmax_xent, REL);
-  m.def("eval_metrics", &eval_metrics, REL);
+  m.def("softmax_xent", &softmax_xent, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("gscale"),
+        py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0);
+  m.def("eval_metrics", &eval_metrics, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("k"),
+        py::arg("out"), py::arg("smoothing") = 0.0);
   m.def("colsum_reduce", &colsum_reduce, REL);
   m.def("allow_knob_changes", [](bool on) { g_knob_tuning.store(on); }, py::arg("on") = true);
   m.def("knobs_frozen", []() { return g_launched.load() && !g_knob_tuning.load(); });

@@ -728,8 +728,15 @@ const char* colsum_reduce_launch(const float* part, const ColRedLayer* layers_de
 // One wave per example.  loss += logsumexp - logit[label]; dlogits = (softmax - onehot)*gscale
 // written as bf16 into [B][ldd] (columns >= ncls zeroed: they are the K padding of the head
 // dgrad); correct += (first argmax == label).
+// SMOOTH (label smoothing eps > 0): the target is t_j = keep*[j == label] + spread with
+// keep = 1 - eps, spread = eps/ncls; dlogits = (softmax - t)*gscale and
+// loss += log(se) + keep*(mx - logit[label]) + spread*sum_j (mx - logit[j]): three non-negative
+// terms, the last summed in the exp loop (no further pass over the row).  SMOOTH = false is the
+// one-hot arithmetic, unchanged.
+template <bool SMOOTH>
 __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
-                                    int B, int ncls, float gscale, bf16_t* __restrict__ dl, int ldd,
+                                    int B, int ncls, float gscale, float keep, float spread,
+                                    bf16_t* __restrict__ dl, int ldd,
                                     float* __restrict__ loss_sum, float* __restrict__ correct) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -747,27 +754,47 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, c
     const int oa = __shfl_xor(amax, o, 64);
     if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
   }
-  float se = 0.f;
-  for (int j = lane; j < ncls; j += 64) se += __expf(row[j] - mx);
+  float se = 0.f, below = 0.f;   // below: sum_j (mx - logit[j]), SMOOTH only
+  for (int j = lane; j < ncls; j += 64) {
+    const float v = row[j];
+    se += __expf(v - mx);
+    if (SMOOTH) below += mx - v;
+  }
   se = warp_sum(se);
+  if (SMOOTH) below = warp_sum(below);
   const int lab = (int)labels[b];
   const float inv = 1.f / se;
   for (int j = lane; j < ldd; j += 64) {
     float d = 0.f;
-    if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
+    if (SMOOTH) {
+      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? keep + spread : spread)) * gscale;
+    } else {
+      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
+    }
     dl[(long)b * ldd + j] = f2bf(d);
   }
   if (lane == 0) {
-    const float lse = mx + __logf(se);
-    unsafeAtomicAdd(loss_sum, lse - row[lab]);
+    if (SMOOTH) {
+      unsafeAtomicAdd(loss_sum, __logf(se) + keep * (mx - row[lab]) + spread * below);
+    } else {
+      const float lse = mx + __logf(se);
+      unsafeAtomicAdd(loss_sum, lse - row[lab]);
+    }
     unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
   }
 }
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
-                                uint16_t* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s) {
+                                uint16_t* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
+                                float smoothing) {
   if (ldd < ncls) return "softmax_xent: ldd < ncls";
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, gscale,
-                     dlogits, ldd, loss_sum, correct);
+  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "softmax_xent: smoothing outside [0, 1]";
+  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
+  if (smoothing > 0.f)
+    hipLaunchKernelGGL(softmax_xent_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
+                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
+  else
+    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
+                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -777,8 +804,10 @@ const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* lab
 // rank = #{j < ncls : logit[j] > logit[label] or (logit[j] == logit[label] and j < label)}
 // (equal logits ordered by index, so rank == 0 is softmax_xent's "first argmax == label");
 // out[1] += (rank == 0); out[2] += (rank < k).  Columns >= ncls of a row are never read.
+// SMOOTH: the loss of softmax_xent_kernel<true> (same terms, same order).
+template <bool SMOOTH>
 __global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
-                                    int B, int ncls, int k, float* __restrict__ out) {
+                                    int B, int ncls, int k, float keep, float spread, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (b >= B) return;
@@ -794,21 +823,34 @@ __global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, c
   mx = warp_max(mx);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
-  float se = 0.f;
-  for (int j = lane; j < ncls; j += 64) se += __expf(row[j] - mx);
+  float se = 0.f, below = 0.f;
+  for (int j = lane; j < ncls; j += 64) {
+    const float v = row[j];
+    se += __expf(v - mx);
+    if (SMOOTH) below += mx - v;
+  }
   se = warp_sum(se);
+  if (SMOOTH) below = warp_sum(below);
   if (lane == 0) {
-    unsafeAtomicAdd(out + 0, mx + __logf(se) - vl);
+    if (SMOOTH) unsafeAtomicAdd(out + 0, __logf(se) + keep * (mx - vl) + spread * below);
+    else unsafeAtomicAdd(out + 0, mx + __logf(se) - vl);
     unsafeAtomicAdd(out + 1, rank == 0 ? 1.f : 0.f);
     unsafeAtomicAdd(out + 2, rank < k ? 1.f : 0.f);
   }
 }
 const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k, float* out,
-                                hipStream_t s) {
+                                hipStream_t s, float smoothing) {
   if (k < 1) return "eval_metrics: k < 1";
   if (ldl < ncls) return "eval_metrics: ldl < ncls";
+  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "eval_metrics: smoothing outside [0, 1]";
   if (B <= 0) return nullptr;
-  hipLaunchKernelGGL(eval_metrics_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, k, out);
+  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
+  if (smoothing > 0.f)
+    hipLaunchKernelGGL(eval_metrics_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, k,
+                       keep, spread, out);
+  else
+    hipLaunchKernelGGL(eval_metrics_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, k,
+                       keep, spread, out);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -210,9 +210,12 @@ const char* colsum_f32_launch(const float* g, long M, int C, int ldg, float* out
 }
 
 // ------------------------------------------------------------------------- softmax-xent
-// One wave per example (the bf16 engine's softmax_xent_kernel with fp32 dlogits).
+// One wave per example (the bf16 engine's softmax_xent_kernel with fp32 dlogits; SMOOTH is its
+// label-smoothing form: target keep*[j == label] + spread, keep = 1 - eps, spread = eps/ncls).
+template <bool SMOOTH>
 __global__ void softmax_xent_f32_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
-                                        int B, int ncls, float gscale, float* __restrict__ dl, int ldd,
+                                        int B, int ncls, float gscale, float keep, float spread,
+                                        float* __restrict__ dl, int ldd,
                                         float* __restrict__ loss_sum, float* __restrict__ correct) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -230,26 +233,43 @@ __global__ void softmax_xent_f32_kernel(const float* __restrict__ logits, int ld
     const int oa = __shfl_xor(amax, o, 64);
     if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
   }
-  float se = 0.f;
-  for (int j = lane; j < ncls; j += 64) se += __expf(row[j] - mx);
+  float se = 0.f, below = 0.f;   // below: sum_j (mx - logit[j]), SMOOTH only
+  for (int j = lane; j < ncls; j += 64) {
+    const float v = row[j];
+    se += __expf(v - mx);
+    if (SMOOTH) below += mx - v;
+  }
   se = warp_sum(se);
+  if (SMOOTH) below = warp_sum(below);
   const int lab = (int)labels[b];
   const float inv = 1.f / se;
   for (int j = lane; j < ldd; j += 64) {
     float d = 0.f;
-    if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
+    if (SMOOTH) {
+      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? keep + spread : spread)) * gscale;
+    } else {
+      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
+    }
     dl[(long)b * ldd + j] = d;
   }
   if (lane == 0) {
-    unsafeAtomicAdd(loss_sum, mx + __logf(se) - row[lab]);
+    if (SMOOTH) unsafeAtomicAdd(loss_sum, __logf(se) + keep * (mx - row[lab]) + spread * below);
+    else unsafeAtomicAdd(loss_sum, mx + __logf(se) - row[lab]);
     unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
   }
 }
 const char* softmax_xent_f32_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
-                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s) {
+                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
+                                    float smoothing) {
   if (ldd < ncls) return "softmax_xent_f32: ldd < ncls";
-  hipLaunchKernelGGL(softmax_xent_f32_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls, gscale,
-                     dlogits, ldd, loss_sum, correct);
+  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "softmax_xent_f32: smoothing outside [0, 1]";
+  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
+  if (smoothing > 0.f)
+    hipLaunchKernelGGL(softmax_xent_f32_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
+                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
+  else
+    hipLaunchKernelGGL(softmax_xent_f32_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
+                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
   return last_err();
 }
 

@@ -150,7 +150,8 @@ const char* gap_bwd_f32_launch(const float* gp, const float* ymask, float* g, in
                                hipStream_t s);
 const char* colsum_f32_launch(const float* g, long M, int C, int ldg, float* out, hipStream_t s);
 const char* softmax_xent_f32_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
-                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s);
+                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
+                                    float smoothing = 0.f);
 
 // ---- elementwise / reduction kernels (eltwise.hip) ----
 struct StemParams {
@@ -257,10 +258,12 @@ const char* colsum_reduce_launch(const float* part, const ColRedLayer* layers_de
 int maxpool_bwd_partial_rows(int B, int H, int W, int C);
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
                                 float gscale, uint16_t* dlogits, int ldd, float* loss_sum, float* correct,
-                                hipStream_t s);
+                                hipStream_t s, float smoothing = 0.f);
 // Evaluation head (no dlogits): out[0] += loss sum, out[1] += top-1 hits, out[2] += top-k hits.
+// (smoothing: the label-smoothing eps in [0, 1] of all three loss heads; the target is
+// (1 - eps)*onehot + eps/ncls, and 0 is the plain one-hot cross-entropy)
 const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k,
-                                float* out, hipStream_t s);
+                                float* out, hipStream_t s, float smoothing = 0.f);
 
 // Per-layer parameter preparation after every optimizer step (one launch for all layers).
 struct PrepLayer {

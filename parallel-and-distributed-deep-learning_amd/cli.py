@@ -11,7 +11,7 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import check_accum, config_from_args
+from .config import check_accum, check_loss, config_from_args
 
 
 def _banner(cfg, strategy):
@@ -20,7 +20,8 @@ def _banner(cfg, strategy):
           f"strategy={cfg.strategy}, replicas={strategy.num_replicas_in_sync}, "
           f"per-replica batch={strategy.per_replica_batch}, global batch={strategy.global_batch}, "
           f"accum_steps={cfg.accum_steps}, effective global batch={strategy.global_batch * cfg.accum_steps}, "
-          f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}", flush=True)
+          f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}, "
+          f"label_smoothing={cfg.label_smoothing:g}", flush=True)
 
 
 def model_summary(cfg) -> str:
@@ -39,6 +40,11 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
     from .parallel.strategies import make_strategy
     from .train.trainer import Trainer, default_callbacks
     cfg = config_from_args(preset, argv, extra)
+    try:
+        check_loss(cfg)
+    except ValueError as e:
+        sys.stderr.write(f"{e}\n")
+        return 2
     if cfg.strategy == "ps":
         if cfg.resume:
             # (the PS job's variables and Adam slots live on the PS roles; the reference has no
@@ -130,7 +136,7 @@ def _evaluate(cfg, strategy, trainer) -> int:
               f"{m['top5_accuracy']:.4f} - {m['images']} images - {m['images'] / dt:.1f} img/s", flush=True)
         if cfg.metrics_jsonl:
             rec = {"evaluate": True, **m, "images_per_sec": m["images"] / dt,
-                   "replicas": strategy.num_replicas_in_sync}
+                   "replicas": strategy.num_replicas_in_sync, "label_smoothing": cfg.label_smoothing}
             with open(cfg.metrics_jsonl, "a") as f:
                 f.write(json.dumps(rec) + "\n")
     _leave_process_group()

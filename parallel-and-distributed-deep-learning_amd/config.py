@@ -48,6 +48,9 @@ class TrainConfig:
     adam_eps: float = 1e-7
     lars_eta: float = 1e-3                         # LARS trust coefficient
     lars_eps: float = 0.0                          # LARS: added to the trust ratio's denominator
+    label_smoothing: float = 0.0                   # eps of the loss target (1 - eps) * onehot + eps / num_classes
+                                                   # (Keras CategoricalCrossentropy(label_smoothing)); training,
+                                                   # validation and --evaluate all report this loss
     # training loop
     epochs: int = 50                               # imagenet-resnet50.py:67
     verbose: int = 2
@@ -145,6 +148,14 @@ def check_accum(cfg: TrainConfig) -> None:
                          "asynchronous update on the parameter servers")
 
 
+def check_loss(cfg: TrainConfig) -> None:
+    """--label-smoothing eps: a value outside [0, 1] is a configuration error, raised before
+    anything is built."""
+    eps = cfg.label_smoothing
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps <= 1.0:
+        raise ValueError(f"--label-smoothing must be a number in [0, 1] (got {eps!r})")
+
+
 def make_config(preset: str = "single", **overrides) -> TrainConfig:
     if preset not in PRESETS:
         raise ValueError(f"unknown preset {preset!r}; choose from {sorted(PRESETS)}")
@@ -171,6 +182,9 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--nesterov", action="store_true", default=None, help="SGD: Nesterov momentum")
     a("--lars-eta", type=float, dest="lars_eta", help="LARS trust coefficient")
     a("--lars-eps", type=float, dest="lars_eps", help="LARS: added to the trust ratio's denominator")
+    a("--label-smoothing", type=float, dest="label_smoothing",
+      help="eps in [0, 1]: the loss target is (1 - eps) * onehot + eps / num_classes (0.1 in the large-batch "
+           "recipes); loss, val_loss and --evaluate all report the smoothed loss")
     a("--lr-schedule", choices=["plateau", "poly"], dest="lr_schedule",
       help="plateau: ReduceLROnPlateau (+ the Horovod warm-up); poly: per-step linear warm-up over "
            "--warmup-epochs, then power-2 decay to --lr-end at the last step, computed on the device")

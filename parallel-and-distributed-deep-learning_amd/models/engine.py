@@ -30,7 +30,7 @@ import torch
 from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
-from .resnet50 import BN_EPS, ParamLayout
+from .resnet50 import BN_EPS, ParamLayout, check_label_smoothing
 
 _PREP_FMT = "<6i2q8i"
 STEM_K = 256   # 4x4 taps x 16 channels of the space-to-depth stem
@@ -88,7 +88,10 @@ class HipEngine:
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: int = 224,
                  device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, bitmask: Optional[bool] = None,
-                 grad_ring: Optional[int] = None, graphed=False):
+                 grad_ring: Optional[int] = None, graphed=False, label_smoothing: float = 0.0):
+        # the loss of forward_backward, evaluate and evaluate_topk alike; a launch constant of the
+        # head kernels, so a captured step keeps the value it was captured with
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         self._grad_ring = grad_ring   # None: GRAD_RING_SMALL at batches <= 64, else GRAD_RING
         # graphed: steps replay from HIP graphs -- True: one stream (see TWO_STREAM_MAX_BATCH);
         # "segmented": bucket-segmented graphs (train/graph.py SegmentedStepGraphs) with the weight
@@ -795,7 +798,8 @@ class HipEngine:
         prof.push("step/backward")
         logits = self.logits[:B]
         dl = self.dlogits[:B]
-        N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2])
+        N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                       self.label_smoothing)
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             if not torch.cuda.is_current_stream_capturing():   # (a capture starts synchronized)
                 torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)
@@ -994,7 +998,7 @@ class HipEngine:
         self._forward(images, B, False, None, (0, 0))
         N = self.N
         N.softmax_xent(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
-                       self.stats[1:2])
+                       self.stats[1:2], self.label_smoothing)
         return self.stats
 
     @torch.no_grad()
@@ -1005,7 +1009,7 @@ class HipEngine:
         self.eval_stats.zero_()
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
-        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats)
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing)
         return self.eval_stats
 
 

@@ -304,7 +304,8 @@ class HipEngineBNTrain(HipEngine):
         prof.push("step/backward")
         logits = self.logits[:B]
         dl = self.dlogits[:B]
-        N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2])
+        N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                       self.label_smoothing)
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)
             self._dgrad_ready = None

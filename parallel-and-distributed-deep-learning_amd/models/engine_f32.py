@@ -30,7 +30,7 @@ from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
 from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K
-from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout
+from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 
 
 EPI_PLAIN, EPI_FWD, EPI_DGRAD = 0, 1, 2
@@ -46,7 +46,8 @@ class HipF32Engine:
     BN_MODES = ("frozen",)
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
-                 device="cuda", bn_mode: str = "frozen", num_classes: int = 1000):
+                 device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, label_smoothing: float = 0.0):
+        self.label_smoothing = check_label_smoothing(label_smoothing)   # the loss of every head call
         if bn_mode not in self.BN_MODES:
             raise ValueError(f"{type(self).__name__} runs bn_mode {self.BN_MODES[0]!r} "
                              "(HipF32Engine: frozen, the reference's training=False; HipF32EngineBNTrain: train)")
@@ -358,7 +359,8 @@ class HipF32Engine:
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
-        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2])
+        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                           self.label_smoothing)
         bks = buckets if buckets is not None else []
         nb = [0]
 
@@ -479,7 +481,7 @@ class HipF32Engine:
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
         self.N.softmax_xent_f32(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
-                                self.stats[1:2])
+                                self.stats[1:2], self.label_smoothing)
         return self.stats
 
     @torch.no_grad()
@@ -490,7 +492,7 @@ class HipF32Engine:
         self.eval_stats.zero_()
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
-        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats)
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing)
         return self.eval_stats
 
 
@@ -520,9 +522,9 @@ class HipF32EngineBNTrain(HipF32Engine):
     RING = 12   # (fp32 b256: ring 3 / 5 / 8 / 12 / 16 -> 73.4 / 73.1 / 72.3-72.6 / 71.9 / 71.8 ms)
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
-                 device="cuda", bn_mode: str = "train", num_classes: int = 1000):
+                 device="cuda", bn_mode: str = "train", num_classes: int = 1000, label_smoothing: float = 0.0):
         super().__init__(layout, batch, crop=crop, image_size=image_size, device=device, bn_mode=bn_mode,
-                         num_classes=num_classes)
+                         num_classes=num_classes, label_smoothing=label_smoothing)
         assert struct.calcsize(_STAT_FMT) == self.N.BNSTAT_LAYER_BYTES
         f32 = dict(dtype=torch.float32, device=self.device)
         n = self.nch
@@ -682,7 +684,8 @@ class HipF32EngineBNTrain(HipF32Engine):
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
-        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2])
+        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                           self.label_smoothing)
         bks = buckets if buckets is not None else []
         nb = [0]
 

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout
+from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 
 
 def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[torch.Tensor] = None,
@@ -197,8 +197,10 @@ class TorchEngine:
     """
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, device="cpu", bn_mode="frozen",
-                 num_classes: int = 1000, bf16_points: bool = False, fused_proj: bool = False):
+                 num_classes: int = 1000, bf16_points: bool = False, fused_proj: bool = False,
+                 label_smoothing: float = 0.0):
         self.L = layout
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         self.device = torch.device(device)
         self.batch = batch
         self.crop = crop
@@ -225,7 +227,7 @@ class TorchEngine:
         x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset)
         logits = self.model.logits(p, x, training=True)
         lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum")
+        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
         (loss_sum * gscale).backward()
         with torch.no_grad():
             self.grads.copy_(p.grad)
@@ -242,7 +244,7 @@ class TorchEngine:
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum")
+        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
         return torch.stack([loss_sum, (logits.argmax(1) == lab).sum().float()])
 
     @torch.no_grad()
@@ -254,7 +256,7 @@ class TorchEngine:
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum")
+        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
         vl = logits.gather(1, lab[:, None])
         idx = torch.arange(logits.shape[1], device=logits.device)[None, :]
         rank = ((logits > vl) | ((logits == vl) & (idx < lab[:, None]))).sum(1)

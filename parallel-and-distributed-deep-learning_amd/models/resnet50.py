@@ -192,3 +192,12 @@ class ParamLayout:
 def param_count_keras() -> Dict[str, int]:
     lay = ParamLayout()
     return {"total": lay.count(), "trainable": lay.count(True), "non_trainable": lay.count(False)}
+
+
+def check_label_smoothing(eps) -> float:
+    """The label-smoothing eps of a loss head as a float in [0, 1] (ValueError otherwise): the
+    target is (1 - eps) * onehot + eps / num_classes, and 0 is the plain one-hot cross-entropy."""
+    eps = float(eps)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {eps}")
+    return eps

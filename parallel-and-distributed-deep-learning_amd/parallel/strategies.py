@@ -86,14 +86,17 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
             graphed = cfg.graphs is True
         return make_hip_engine(L, cap, bn_mode=cfg.bn_mode, crop=cfg.crop, image_size=cfg.image_size,
                                device=device, num_classes=cfg.num_classes,
-                               grad_ring=HipEngine.GRAD_RING if graphed else None, graphed=graphed)
+                               grad_ring=HipEngine.GRAD_RING if graphed else None, graphed=graphed,
+                               label_smoothing=cfg.label_smoothing)
     if device.type == "cuda":
         from ..models.engine_f32 import HipF32Engine, HipF32EngineBNTrain
         # frozen: the reference's configuration; train: batch statistics (both explicit fp32 schedules)
         cls = HipF32Engine if cfg.bn_mode == "frozen" else HipF32EngineBNTrain
-        return cls(L, cap, crop=cfg.crop, image_size=cfg.image_size, device=device, num_classes=cfg.num_classes)
+        return cls(L, cap, crop=cfg.crop, image_size=cfg.image_size, device=device, num_classes=cfg.num_classes,
+                   label_smoothing=cfg.label_smoothing)
     from ..models.reference import TorchEngine
-    return TorchEngine(L, cap, crop=cfg.crop, device=device, bn_mode=cfg.bn_mode, num_classes=cfg.num_classes)
+    return TorchEngine(L, cap, crop=cfg.crop, device=device, bn_mode=cfg.bn_mode, num_classes=cfg.num_classes,
+                       label_smoothing=cfg.label_smoothing)
 
 
 class Augment:
@@ -120,8 +123,9 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
-        from ..config import check_accum
+        from ..config import check_accum, check_loss
         check_accum(cfg)
+        check_loss(cfg)
         self.cfg = cfg
         self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
         self.rank = 0

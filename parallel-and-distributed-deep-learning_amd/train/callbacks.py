@@ -228,6 +228,8 @@ class JsonlLogger(Callback):
         k = getattr(self.trainer.cfg, "accum_steps", 1)
         rec["accum_steps"] = k
         rec["effective_global_batch"] = self.trainer.strategy.global_batch * k
+        # (loss and val_loss above are the smoothed loss of this eps)
+        rec["label_smoothing"] = float(getattr(self.trainer.cfg, "label_smoothing", 0.0))
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)
