@@ -461,9 +461,9 @@ void softmax_xent_f32(Tensor logits, Tensor labels, int64_t ncls, double gscale,
                       Tensor correct, double smoothing) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
   PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "softmax_xent_f32: smoothing must be in [0, 1]");
-  ok(pddl::softmax_xent_f32_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
-                                   (int)ncls, (float)gscale, f32p(dlogits), ld(dlogits), f32p(loss_sum),
-                                   f32p(correct), cur_stream(), (float)smoothing),
+  ok(pddl::softmax_xent_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
+                               (int)ncls, (float)gscale, f32p(dlogits), ld(dlogits), f32p(loss_sum),
+                               f32p(correct), cur_stream(), (float)smoothing),
      "softmax_xent_f32");
 }
 void prep_f32(Tensor params, Tensor table, int64_t nlayers, Tensor wf32, Tensor scale, Tensor shift, double eps) {

@@ -6,7 +6,8 @@
 //                    (gather form, fused with the ReLU mask of conv1's output)  (N6)
 //   * gap          : GlobalAveragePooling2D forward / backward (+ ReLU mask)   (N7)
 //   * colsum       : per-channel sum of a gradient (BN beta / conv-bias grads)
-//   * softmax_xent : softmax + sparse categorical cross-entropy + accuracy, fwd+bwd fused (N9)
+//   * softmax_xent : softmax + sparse categorical cross-entropy + accuracy, fwd+bwd fused (N9),
+//                    bf16 or fp32 dlogits; eval_metrics: its loss with top-1 / top-k hits, no dlogits
 //   * prep / wgrad_finalize / bn_grad : frozen-BN folding and per-channel parameter grads (N4)
 // Every kernel moves 16 bytes per lane (8 x bf16) where the layout allows (Guideline 13).
 #include "common.h"
@@ -733,10 +734,37 @@ const char* colsum_reduce_launch(const float* part, const ColRedLayer* layers_de
 // loss += log(se) + keep*(mx - logit[label]) + spread*sum_j (mx - logit[j]): three non-negative
 // terms, the last summed in the exp loop (no further pass over the row).  SMOOTH = false is the
 // one-hot arithmetic, unchanged.
+// T: the type of dlogits -- bf16_t (the bf16 engines) or float (the fp32 engines, ldd >= ncls).
+// The evaluation head (eval_metrics_kernel, below) shares the two helpers.
+template <typename T> __device__ __forceinline__ T wcvt(float v);
+template <> __device__ __forceinline__ uint16_t wcvt<uint16_t>(float v) { return f2bf(v); }
+template <> __device__ __forceinline__ float wcvt<float>(float v) { return v; }
+
+// The pass over a row once its maximum is known: se = sum_j exp(logit[j] - mx) and, SMOOTH
+// only, below = sum_j (mx - logit[j]), both summed over the wave.
 template <bool SMOOTH>
+__device__ __forceinline__ void head_row_sums(const float* __restrict__ row, int ncls, int lane, float mx, float& se,
+                                              float& below) {
+  se = 0.f, below = 0.f;
+  for (int j = lane; j < ncls; j += 64) {
+    const float v = row[j];
+    se += __expf(v - mx);
+    if (SMOOTH) below += mx - v;
+  }
+  se = warp_sum(se);
+  if (SMOOTH) below = warp_sum(below);
+}
+// The loss of one row (vl: the label's logit).
+template <bool SMOOTH>
+__device__ __forceinline__ float head_row_loss(float mx, float se, float below, float vl, float keep, float spread) {
+  if (SMOOTH) return __logf(se) + keep * (mx - vl) + spread * below;
+  return mx + __logf(se) - vl;
+}
+
+template <typename T, bool SMOOTH>
 __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
                                     int B, int ncls, float gscale, float keep, float spread,
-                                    bf16_t* __restrict__ dl, int ldd,
+                                    T* __restrict__ dl, int ldd,
                                     float* __restrict__ loss_sum, float* __restrict__ correct) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -754,14 +782,8 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, c
     const int oa = __shfl_xor(amax, o, 64);
     if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
   }
-  float se = 0.f, below = 0.f;   // below: sum_j (mx - logit[j]), SMOOTH only
-  for (int j = lane; j < ncls; j += 64) {
-    const float v = row[j];
-    se += __expf(v - mx);
-    if (SMOOTH) below += mx - v;
-  }
-  se = warp_sum(se);
-  if (SMOOTH) below = warp_sum(below);
+  float se, below;
+  head_row_sums<SMOOTH>(row, ncls, lane, mx, se, below);
   const int lab = (int)labels[b];
   const float inv = 1.f / se;
   for (int j = lane; j < ldd; j += 64) {
@@ -771,32 +793,42 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, c
     } else {
       if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
     }
-    dl[(long)b * ldd + j] = f2bf(d);
+    dl[(long)b * ldd + j] = wcvt<T>(d);
   }
   if (lane == 0) {
-    if (SMOOTH) {
-      unsafeAtomicAdd(loss_sum, __logf(se) + keep * (mx - row[lab]) + spread * below);
-    } else {
-      const float lse = mx + __logf(se);
-      unsafeAtomicAdd(loss_sum, lse - row[lab]);
-    }
+    unsafeAtomicAdd(loss_sum, head_row_loss<SMOOTH>(mx, se, below, row[lab], keep, spread));
     unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
   }
 }
+namespace {
+bool smoothing_ok(float eps) { return eps >= 0.f && eps <= 1.f; }   // (false for a NaN)
+
+template <typename T>
+const char* softmax_xent_launch_t(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
+                                  T* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
+                                  float smoothing) {
+  if (ldd < ncls) return "softmax_xent: ldd < ncls";
+  if (!smoothing_ok(smoothing)) return "softmax_xent: smoothing outside [0, 1]";
+  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
+  if (smoothing > 0.f)
+    hipLaunchKernelGGL((softmax_xent_kernel<T, true>), dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B,
+                       ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct);
+  else
+    hipLaunchKernelGGL((softmax_xent_kernel<T, false>), dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B,
+                       ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+}  // namespace
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
                                 uint16_t* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
                                 float smoothing) {
-  if (ldd < ncls) return "softmax_xent: ldd < ncls";
-  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "softmax_xent: smoothing outside [0, 1]";
-  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
-  if (smoothing > 0.f)
-    hipLaunchKernelGGL(softmax_xent_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
-                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
-  else
-    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
-                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing);
+}
+const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
+                                float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
+                                float smoothing) {
+  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing);
 }
 
 // ---------------------------------------------------------------------- eval-metrics
@@ -804,7 +836,7 @@ const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* lab
 // rank = #{j < ncls : logit[j] > logit[label] or (logit[j] == logit[label] and j < label)}
 // (equal logits ordered by index, so rank == 0 is softmax_xent's "first argmax == label");
 // out[1] += (rank == 0); out[2] += (rank < k).  Columns >= ncls of a row are never read.
-// SMOOTH: the loss of softmax_xent_kernel<true> (same terms, same order).
+// SMOOTH: the loss of softmax_xent_kernel<T, true> (the same helpers: same terms, same order).
 template <bool SMOOTH>
 __global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
                                     int B, int ncls, int k, float keep, float spread, float* __restrict__ out) {
@@ -823,17 +855,10 @@ __global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, c
   mx = warp_max(mx);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
-  float se = 0.f, below = 0.f;
-  for (int j = lane; j < ncls; j += 64) {
-    const float v = row[j];
-    se += __expf(v - mx);
-    if (SMOOTH) below += mx - v;
-  }
-  se = warp_sum(se);
-  if (SMOOTH) below = warp_sum(below);
+  float se, below;
+  head_row_sums<SMOOTH>(row, ncls, lane, mx, se, below);
   if (lane == 0) {
-    if (SMOOTH) unsafeAtomicAdd(out + 0, __logf(se) + keep * (mx - vl) + spread * below);
-    else unsafeAtomicAdd(out + 0, mx + __logf(se) - vl);
+    unsafeAtomicAdd(out + 0, head_row_loss<SMOOTH>(mx, se, below, vl, keep, spread));
     unsafeAtomicAdd(out + 1, rank == 0 ? 1.f : 0.f);
     unsafeAtomicAdd(out + 2, rank < k ? 1.f : 0.f);
   }
@@ -842,7 +867,7 @@ const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* lab
                                 hipStream_t s, float smoothing) {
   if (k < 1) return "eval_metrics: k < 1";
   if (ldl < ncls) return "eval_metrics: ldl < ncls";
-  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "eval_metrics: smoothing outside [0, 1]";
+  if (!smoothing_ok(smoothing)) return "eval_metrics: smoothing outside [0, 1]";
   if (B <= 0) return nullptr;
   const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
   if (smoothing > 0.f)
@@ -861,11 +886,7 @@ const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* lab
 // frozen-BN affine a = gamma / sqrt(var + eps), b = (bias - mean) * a + beta.
 // (T = uint16_t: bf16 weights of the bf16 engine; T = float: the fp32 engine, whose forward
 // convs read the fp32 master directly -- only the stem's space-to-depth copy and the dgrad
-// weights are prepared)
-template <typename T> __device__ __forceinline__ T wcvt(float v);
-template <> __device__ __forceinline__ uint16_t wcvt<uint16_t>(float v) { return f2bf(v); }
-template <> __device__ __forceinline__ float wcvt<float>(float v) { return v; }
-
+// weights are prepared; wcvt<T>: above, at the loss head)
 template <typename T>
 __global__ void prep_kernel(const float* __restrict__ prm, const PrepLayer* __restrict__ L, T* __restrict__ wbf,
                             float* __restrict__ scale, float* __restrict__ shift, float eps) {

@@ -1,13 +1,13 @@
 // fp32 elementwise / reduction kernels of the reference-precision engine (models/engine_f32.py):
 // the reference trains in float32 (imagenet-resnet50.py:56-62, no mixed-precision policy), so
-// its max-pool, global-average-pool, softmax cross-entropy and the per-channel column sums run
-// here on fp32 NHWC activations, 16 bytes (4 channels) per lane.
+// its max-pool, global-average-pool and the per-channel column sums run here on fp32 NHWC
+// activations, 16 bytes (4 channels) per lane.  (Its softmax cross-entropy
+// is eltwise.hip's softmax_xent_kernel with fp32 dlogits.)
 //   * maxpool_fwd_f32 : ZeroPadding2D(1) + MaxPooling2D(3, 2), first argmax in scan order -> idx
 //   * maxpool_bwd_f32 : gather form (each input position sums the outputs whose argmax is it),
 //                       fused with the ReLU mask of conv1's output (no atomics)
 //   * gap_fwd_f32 / gap_bwd_f32 (+ ReLU mask of the last block's output, partial column sums)
 //   * colsum_f32      : out[c] += sum_m g[m][c]
-//   * softmax_xent_f32: softmax + sparse categorical CE + accuracy, fp32 dlogits
 #include "common.h"
 #include "kernels.h"
 
@@ -206,70 +206,6 @@ const char* colsum_f32_launch(const float* g, long M, int C, int ldg, float* out
   const long blocks = lmin((M + 255) / 256, 2048);
   const long rpb = (M + blocks - 1) / blocks;
   hipLaunchKernelGGL(colsum_f32_kernel, dim3((int)blocks), dim3(256), 0, s, g, M, C, ldg, rpb, out);
-  return last_err();
-}
-
-// ------------------------------------------------------------------------- softmax-xent
-// One wave per example (the bf16 engine's softmax_xent_kernel with fp32 dlogits; SMOOTH is its
-// label-smoothing form: target keep*[j == label] + spread, keep = 1 - eps, spread = eps/ncls).
-template <bool SMOOTH>
-__global__ void softmax_xent_f32_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
-                                        int B, int ncls, float gscale, float keep, float spread,
-                                        float* __restrict__ dl, int ldd,
-                                        float* __restrict__ loss_sum, float* __restrict__ correct) {
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const float* row = logits + (long)b * ldl;
-  float mx = -INFINITY;
-  int amax = 0x7fffffff;
-  for (int j = lane; j < ncls; j += 64) {
-    const float v = row[j];
-    if (v > mx) { mx = v; amax = j; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(mx, o, 64);
-    const int oa = __shfl_xor(amax, o, 64);
-    if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
-  }
-  float se = 0.f, below = 0.f;   // below: sum_j (mx - logit[j]), SMOOTH only
-  for (int j = lane; j < ncls; j += 64) {
-    const float v = row[j];
-    se += __expf(v - mx);
-    if (SMOOTH) below += mx - v;
-  }
-  se = warp_sum(se);
-  if (SMOOTH) below = warp_sum(below);
-  const int lab = (int)labels[b];
-  const float inv = 1.f / se;
-  for (int j = lane; j < ldd; j += 64) {
-    float d = 0.f;
-    if (SMOOTH) {
-      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? keep + spread : spread)) * gscale;
-    } else {
-      if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
-    }
-    dl[(long)b * ldd + j] = d;
-  }
-  if (lane == 0) {
-    if (SMOOTH) unsafeAtomicAdd(loss_sum, __logf(se) + keep * (mx - row[lab]) + spread * below);
-    else unsafeAtomicAdd(loss_sum, mx + __logf(se) - row[lab]);
-    unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
-  }
-}
-const char* softmax_xent_f32_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
-                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
-                                    float smoothing) {
-  if (ldd < ncls) return "softmax_xent_f32: ldd < ncls";
-  if (!(smoothing >= 0.f && smoothing <= 1.f)) return "softmax_xent_f32: smoothing outside [0, 1]";
-  const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
-  if (smoothing > 0.f)
-    hipLaunchKernelGGL(softmax_xent_f32_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
-                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
-  else
-    hipLaunchKernelGGL(softmax_xent_f32_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B, ncls,
-                       gscale, keep, spread, dlogits, ldd, loss_sum, correct);
   return last_err();
 }
 

@@ -149,9 +149,6 @@ const char* gap_fwd_f32_launch(const float* x, float* y, int B, int HW, int C, h
 const char* gap_bwd_f32_launch(const float* gp, const float* ymask, float* g, int B, int HW, int C, float* colsum_rows,
                                hipStream_t s);
 const char* colsum_f32_launch(const float* g, long M, int C, int ldg, float* out, hipStream_t s);
-const char* softmax_xent_f32_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
-                                    float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
-                                    float smoothing = 0.f);
 
 // ---- elementwise / reduction kernels (eltwise.hip) ----
 struct StemParams {
@@ -256,8 +253,13 @@ struct ColRedLayer { long part; int rows, C, out; int pad; };   // pad > 0: row 
 const char* colsum_reduce_launch(const float* part, const ColRedLayer* layers_dev, int nlayers, float* colsum,
                                  hipStream_t s);
 int maxpool_bwd_partial_rows(int B, int H, int W, int C);
+// The training head, one kernel for both precisions: bf16 dlogits (the bf16 engines; columns
+// ncls..ldd zeroed) or fp32 dlogits (the fp32 engines).
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
                                 float gscale, uint16_t* dlogits, int ldd, float* loss_sum, float* correct,
+                                hipStream_t s, float smoothing = 0.f);
+const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
+                                float gscale, float* dlogits, int ldd, float* loss_sum, float* correct,
                                 hipStream_t s, float smoothing = 0.f);
 // Evaluation head (no dlogits): out[0] += loss sum, out[1] += top-1 hits, out[2] += top-k hits.
 // (smoothing: the label-smoothing eps in [0, 1] of all three loss heads; the target is

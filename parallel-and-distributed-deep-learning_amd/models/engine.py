@@ -31,6 +31,7 @@ from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
 from .resnet50 import BN_EPS, ParamLayout, check_label_smoothing
+from .side_stream import SideStream
 
 _PREP_FMT = "<6i2q8i"
 STEM_K = 256   # 4x4 taps x 16 channels of the space-to-depth stem
@@ -48,7 +49,7 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
-class HipEngine:
+class HipEngine(SideStream):
     BN_MODES = ("frozen",)   # HipEngineBNTrain (models/engine_bn.py) runs bn_mode="train"
     FUSE_PROJ_OK = True     # projection blocks: conv3 + shortcut conv as one dual-source GEMM
     FUSE_BWD_OK = True      # stage-2/3 conv3 backward: dgrad + wgrad in one launch (bwd1x1.hip)
@@ -99,7 +100,6 @@ class HipEngine:
         self.graphed = bool(graphed)
         self.defer_side = (graphed == "segmented" and bool(opt(E, "seg_side", True)) and self.TWO_STREAM_OK
                            and self.DEFER_OK)
-        self._defer = None            # capture-time list of deferred side-stream closures
         if bn_mode not in self.BN_MODES:
             raise ValueError(f"{type(self).__name__} runs bn_mode in {self.BN_MODES}, not {bn_mode!r} "
                              "(use make_hip_engine)")
@@ -192,9 +192,7 @@ class HipEngine:
         # gradients run on a side stream concurrently with the data-gradient chain.
         # PDDL_ENGINE two_stream=1 / 0 forces it; default on up to TWO_STREAM_MAX_BATCH images.
         self.two_stream = self._two_stream_wanted(batch)
-        self.side = torch.cuda.Stream(dev) if self.two_stream and dev.type == "cuda" else None
-        self._pending, self._last_side = {}, None
-        self._evpool, self._evi = [], 0   # fork/join events (see _event)
+        self._init_side(dev, self.two_stream)
         self._prep_evs, self._dgrad_ready = None, None   # (after_update's dgrad-weight fork)
 
     # ------------------------------------------------------------------ tables
@@ -682,103 +680,12 @@ class HipEngine:
         return lab
 
     # ------------------------------------------------------------------ two-stream backward
+    # (the scheduler -- _side_run, _before_write, _bucket_ready, _join_side -- is the SideStream mixin)
     def _two_stream_wanted(self, batch) -> bool:
         ts = opt(E, "two_stream", "auto")
         if ts != "auto":
             return self.TWO_STREAM_OK and ts == "1"
         return self.TWO_STREAM_OK and batch <= self.TWO_STREAM_MAX_BATCH and (not self.graphed or self.defer_side)
-
-    def _event(self):
-        """The next fork/join event of this step, from a pool the engine owns for its whole
-        life: the i-th record of every step reuses the i-th event (a wait binds to the record
-        made before it, so reuse after the wait is safe), so a step -- eager or captured --
-        creates and destroys no HIP events."""
-        i = self._evi
-        self._evi += 1
-        if i == len(self._evpool):
-            self._evpool.append(torch.cuda.Event())
-        return self._evpool[i]
-
-    def _side_run(self, fn, *args, reads=()):
-        """Launch a weight-gradient kernel on the side stream, ordered after everything enqueued
-        on the compute stream so far; `reads` names the gradient buffers it reads, which the
-        compute stream must not overwrite before it is done (see _before_write).
-
-        Deferred (a segmented capture, begin_defer): the call is queued instead, and the capture
-        records the queue of each segment as a single-stream side graph that the replay runs
-        after that segment's main graph, concurrently with the next segment.  No fork / join
-        events inside any graph (the runtime launches single-stream graphs from pre-built packets;
-        its multi-branch launch path faults: train/graph.py replay_stream), and no buffer hazards:
-        the deferred engine's gradient buffers are never reused within a step (_alloc_acts)."""
-        if self._defer is not None:
-            self._defer.append((fn, args))
-            return
-        if self.side is None:
-            fn(*args)
-            return
-        main = torch.cuda.current_stream(self.device)
-        ev = self._event()
-        ev.record(main)
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            fn(*args)
-        done = self._event()
-        done.record(self.side)
-        for r in reads:
-            self._pending[r] = done
-        self._last_side = done
-
-    def _before_write(self, *bufs):
-        """The compute stream is about to overwrite these gradient buffers: wait for the side
-        stream's last reader of each."""
-        if self.side is None or self._defer is not None:
-            return
-        main = torch.cuda.current_stream(self.device)
-        for b in bufs:
-            ev = self._pending.pop(b, None)
-            if ev is not None:
-                main.wait_event(ev)
-
-    def _bucket_ready(self, cb, i):
-        """Report bucket i complete.  Two streams: its gradients come from both streams, so the
-        side stream first waits for the compute stream and the callback runs with the SIDE stream
-        current -- whatever it enqueues or records (an all-reduce, an optimizer update) is
-        ordered after both, and the compute stream never blocks on the side stream."""
-        if self.side is None or self._defer is not None:
-            cb(i)
-            return
-        if getattr(cb, "needs_join", False):   # (e.g. a graph capture cut at the bucket boundary)
-            self._join_side()
-            cb(i)
-            return
-        ev = self._event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            cb(i)
-        done = self._event()
-        done.record(self.side)
-        self._last_side = done
-
-    def begin_defer(self):
-        """Queue side-stream work from now on (segmented capture; take_deferred drains it)."""
-        assert self.side is not None and self.defer_side
-        self._defer = []
-
-    def take_deferred(self):
-        q, self._defer = self._defer, []
-        return q
-
-    def end_defer(self):
-        left, self._defer = self._defer, None
-        assert not left, "deferred side work left uncaptured"
-
-    def _join_side(self):
-        if self.side is None or self._last_side is None:
-            return
-        torch.cuda.current_stream(self.device).wait_event(self._last_side)
-        self._pending.clear()
-        self._last_side = None
 
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
@@ -786,8 +693,7 @@ class HipEngine:
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
-        self._pending, self._last_side = {}, None
-        self._evi = 0
+        self._side_begin_step()
         # (clearing the workspace on the side stream under the forward measured no gain at b32:
         # 3.604-3.624 vs 3.602-3.606 ms, round 6)
         self.ws.zero_()

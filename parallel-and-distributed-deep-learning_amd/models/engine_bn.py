@@ -309,8 +309,7 @@ class HipEngineBNTrain(HipEngine):
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)
             self._dgrad_ready = None
-        self._pending, self._last_side = {}, None
-        self._evi = 0
+        self._side_begin_step()
         bks = buckets if buckets is not None else []
         nb = [0]
 
@@ -332,7 +331,7 @@ class HipEngineBNTrain(HipEngine):
         gout = self.gbuf[cur][: B * H5 * H5 * 2048].view(B, H5, H5, 2048)
         N.gap_bwd(dpooled, x5, gout, None)
         s2 = self._s2_fed()
-        # weight gradients on the side stream (HipEngine._side_run), BN backward and data gradients
+        # weight gradients on the side stream (SideStream._side_run), BN backward and data gradients
         # on the compute stream; ("g", i) / ("s2", bi) / ("z3", j) / ("g2", j) / ("g1", j): gradient
         # buffers a side launch reads, waited for before the compute stream rewrites them
         for bi in range(len(blocks) - 1, -1, -1):

@@ -31,6 +31,7 @@ from ..utils import profiling as prof
 from ..utils.envopts import opt
 from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
+from .side_stream import SideStream
 
 
 EPI_PLAIN, EPI_FWD, EPI_DGRAD = 0, 1, 2
@@ -40,7 +41,7 @@ def _rows64(m: int) -> int:
     return (m + 63) // 64
 
 
-class HipF32Engine:
+class HipF32Engine(SideStream):
     """Explicit-schedule fp32 engine (frozen BN).  Interface of HipEngine / TorchEngine: flat
     fp32 `params` / `grads`, `init`, `after_update`, `forward_backward`, `evaluate`."""
     BN_MODES = ("frozen",)
@@ -173,7 +174,7 @@ class HipF32Engine:
             outer = max(outer, B * H * H * b.cin, B * Ho * Ho * 4 * f)
             H = Ho
         self.H5 = H
-        # two-stream backward (weight gradients on a side stream, HipF32Engine._side_run): the
+        # two-stream backward (weight gradients on a side stream, SideStream._side_run): the
         # gradient buffers are rings deep enough for the data-gradient chain to run a few
         # blocks ahead of the weight gradients still reading older ones
         self.two_stream = self._two_stream_wanted(B)
@@ -182,8 +183,7 @@ class HipF32Engine:
         self.g1bufs = [torch.empty(inner, **f32) for _ in range(D)]
         self.g2bufs = [torch.empty(inner, **f32) for _ in range(D)]
         self.g1buf, self.g2buf = self.g1bufs[0], self.g2bufs[0]
-        self.side = torch.cuda.Stream(dev) if self.two_stream and dev.type == "cuda" else None
-        self._evpool, self._evi = [], 0
+        self._init_side(dev, self.two_stream)
         self.tmp = torch.empty(tmp, **f32)
         # split-K workspace of the underfilled conv / dgrad problems (conv_f32.hip: small batches),
         # this engine's own (N.splitk_use makes it current for the launching thread)
@@ -229,6 +229,7 @@ class HipF32Engine:
         return res
 
     # ------------------------------------------------------------------ two-stream backward
+    # (the scheduler -- _side_run, _before_write, _join_side -- is the SideStream mixin)
     TWO_STREAM_MAX_BATCH = 1024
     RING = 5   # (fp32 b256: ring 2 / 3 / 5 / 8 -> 59.9 / 59.3 / 58.4 / 58.5 ms; one stream 61.9)
 
@@ -237,48 +238,6 @@ class HipF32Engine:
         if ts != "auto":
             return ts == "1"
         return batch <= self.TWO_STREAM_MAX_BATCH
-
-    def _event(self):
-        """The i-th fork / join event of every step reuses one pooled event (a wait binds to the
-        record made before it), so a step creates no HIP events."""
-        i = self._evi
-        self._evi += 1
-        if i == len(self._evpool):
-            self._evpool.append(torch.cuda.Event())
-        return self._evpool[i]
-
-    def _side_run(self, fn, *args, reads=()):
-        """fn(*args) on the side stream after everything enqueued on the compute stream so far;
-        `reads`: the gradient buffers it reads, which the compute stream must not overwrite
-        before it is done (_before_write)."""
-        if self.side is None:
-            fn(*args)
-            return
-        ev = self._event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            fn(*args)
-        done = self._event()
-        done.record(self.side)
-        for r in reads:
-            self._pending[r] = done
-        self._last_side = done
-
-    def _before_write(self, *bufs):
-        if self.side is None:
-            return
-        main = torch.cuda.current_stream(self.device)
-        for b in bufs:
-            ev = self._pending.pop(b, None)
-            if ev is not None:
-                main.wait_event(ev)
-
-    def _join_side(self):
-        if self.side is not None and self._last_side is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._last_side)
-            self._pending.clear()
-            self._last_side = None
 
     # ------------------------------------------------------------------ params
     def init(self, seed=0):
@@ -370,7 +329,7 @@ class HipF32Engine:
                 nb[0] += 1
 
         # ---- head
-        self._pending, self._last_side, self._evi = {}, None, 0
+        self._side_begin_step()
         pooled = self.pooled[:B]
         chd = self.ch["dense"]
         N.wgrad_f32(pooled.view(B, 1, 1, 2048), 1, 1, 1, 0, dl.view(B, 1, 1, ncls), self._gv("dense", ncls, 2048))
@@ -695,7 +654,7 @@ class HipF32EngineBNTrain(HipF32Engine):
                 nb[0] += 1
 
         # ---- head: Dense wgrad, bias gradient (column sums), dgrad into the pooled features
-        self._pending, self._last_side, self._evi = {}, None, 0
+        self._side_begin_step()
         pooled = self.pooled[:B]
         chd = self.ch["dense"]
         N.wgrad_f32(pooled.view(B, 1, 1, 2048), 1, 1, 1, 0, dl.view(B, 1, 1, ncls), self._gv("dense", ncls, 2048))
@@ -712,7 +671,7 @@ class HipF32EngineBNTrain(HipF32Engine):
         W = self._side_run
         gout = self.gbuf[cur][: B * H5 * H5 * 2048].view(B, H5, H5, 2048)
         N.gap_bwd_f32(dpooled, x5, gout, None)
-        # weight gradients on the side stream (HipF32Engine._side_run), BN backward and data
+        # weight gradients on the side stream (SideStream._side_run), BN backward and data
         # gradients on the compute stream; ("g", i) / ("s2", bi) / ("z3", j) / ("g2", j) / ("g1", j):
         # gradient buffers a side launch reads, waited for before the compute stream rewrites them
         for bi in range(len(bl) - 1, -1, -1):
