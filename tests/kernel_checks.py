@@ -2,7 +2,9 @@
 
 Output buffers start out as a non-canonical NaN bit pattern (`sent`), so a test can tell both that
 every element a kernel owns was written and that nothing else was touched; `okey` / `ulps` measure
-distances in units in the last place, `table` packs a launch table the way the engines do.
+distances in units in the last place, `table` packs a launch table the way the engines do;
+`pack_bits`, `pool_ref` and `pool_bwd_ref` are the plain references of the ReLU bit masks and of
+the 3x3 / stride-2 max-pool that several kernels fuse.
 """
 import torch
 
@@ -80,3 +82,37 @@ class ByteOut:
     def check(self, what):
         assert bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.n:] == 0xA5).all()), \
             f"{what}: bits guard overwritten"
+
+
+def pack_bits(y):
+    w = (y.float() > 0).reshape(-1, 8).to(torch.int32)
+    return (w << torch.arange(8, device=dev, dtype=torch.int32)).sum(-1).to(torch.uint8)
+
+
+def pool_ref(x):
+    """ZeroPadding2D(1) + 3x3 / stride 2 by a scan over the nine taps with strict '>': the first
+    maximum in scan order wins.  x [B, H, W, C] (any float type; compared in fp64)."""
+    B, H, W, C = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    xp = torch.zeros(B, H + 2, W + 2, C, dtype=torch.float64, device=dev)
+    xp[:, 1:H + 1, 1:W + 1] = x.double()
+    best = torch.full((B, Ho, Wo, C), float("-inf"), dtype=torch.float64, device=dev)
+    tap = torch.zeros(B, Ho, Wo, C, dtype=torch.uint8, device=dev)
+    for r in range(3):
+        for s in range(3):
+            v = xp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2]
+            up = v > best
+            best = torch.where(up, v, best)
+            tap = torch.where(up, torch.full_like(tap, r * 3 + s), tap)
+    return best, tap
+
+
+def pool_bwd_ref(gy, tap, xmask, H, W):
+    """Route each output gradient to its tap; taps in the padding are dropped; ReLU mask of x."""
+    B, Ho, Wo, C = gy.shape
+    gp = torch.zeros(B, H + 2, W + 2, C, dtype=torch.float64, device=dev)
+    for r in range(3):
+        for s in range(3):
+            gp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += torch.where(tap == r * 3 + s, gy.double(), 0.0)
+    gx = gp[:, 1:H + 1, 1:W + 1]
+    return gx if xmask is None else gx * (xmask.double() > 0)

@@ -21,7 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kernel_checks import ByteOut, Out, U, dev, rel64
+from kernel_checks import ByteOut, Out, U, dev, pack_bits, pool_bwd_ref, pool_ref, rel64
 
 pytestmark = pytest.mark.gpu
 
@@ -53,46 +53,12 @@ def osize(n):
     return (n - 1) // 2 + 1
 
 
-def pack_bits(y):
-    w = (y.float() > 0).reshape(-1, 8).to(torch.int32)
-    return (w << torch.arange(8, device=dev, dtype=torch.int32)).sum(-1).to(torch.uint8)
-
-
 def same_bits(a, b):
     v = torch.int16 if a.element_size() == 2 else torch.int32
     return torch.equal(a.contiguous().view(v), b.contiguous().view(v))
 
 
 # ------------------------------------------------------------------------------ max-pool
-def pool_ref(x):
-    """ZeroPadding2D(1) + 3x3 / stride 2 by a scan over the nine taps with strict '>': the first
-    maximum in scan order wins.  x [B, H, W, C] (any float type; compared in fp64)."""
-    B, H, W, C = x.shape
-    Ho, Wo = osize(H), osize(W)
-    xp = torch.zeros(B, H + 2, W + 2, C, dtype=torch.float64, device=dev)
-    xp[:, 1:H + 1, 1:W + 1] = x.double()
-    best = torch.full((B, Ho, Wo, C), float("-inf"), dtype=torch.float64, device=dev)
-    tap = torch.zeros(B, Ho, Wo, C, dtype=torch.uint8, device=dev)
-    for r in range(3):
-        for s in range(3):
-            v = xp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2]
-            up = v > best
-            best = torch.where(up, v, best)
-            tap = torch.where(up, torch.full_like(tap, r * 3 + s), tap)
-    return best, tap
-
-
-def pool_bwd_ref(gy, tap, xmask, H, W):
-    """Route each output gradient to its tap; taps in the padding are dropped; ReLU mask of x."""
-    B, Ho, Wo, C = gy.shape
-    gp = torch.zeros(B, H + 2, W + 2, C, dtype=torch.float64, device=dev)
-    for r in range(3):
-        for s in range(3):
-            gp[:, r:r + 2 * Ho - 1:2, s:s + 2 * Wo - 1:2] += torch.where(tap == r * 3 + s, gy.double(), 0.0)
-    gx = gp[:, 1:H + 1, 1:W + 1]
-    return gx if xmask is None else gx * (xmask.double() > 0)
-
-
 def pad_winner(tap, H, W):
     """Outputs whose winning tap lies in the zero padding."""
     B, Ho, Wo, C = tap.shape

@@ -1,0 +1,639 @@
+"""The hand-written matrix-core kernels of the stem and of stage 2 (csrc/kernels/conv3x3c64.hip,
+c3c1.hip, stem.hip, bwd1x1.hip) against plain fp64 references, at the smallest shapes at which
+their tiling can go wrong.
+
+  conv3x3c64   forward (with / without bits) and data gradient (partial column sums, idle rows
+               zero): H < 4, W = 1, 61 and 62, a partial last row tile, workgroups capped to 1
+               and 3 so that one walks several tiles across images and both window buffers;
+               W = 63 rejected with nothing written
+  ..._wgrad    the same shapes and caps, dw preloaded, ld_dw = 576 and 640 (pad columns untouched)
+  c3c1         M around the 64-row tile, residual and the two bits outputs given or not; y1
+               against a reference built from the kernel's own (verified) block output
+  stem_pool    forward and backward at crops 8, 28, 36 (pool heights 2, 7, 9) x every row-block
+               argument, crop 248 (the widest the prefetch covers), crop 252 rejected; ties
+               after ReLU exercise the tap scan order, taps into the zero padding the router
+  bwd1x1       plain (both channel pairs, M around the tile, padded wd / dw rows), stride-2
+               (odd and even sides; `out` owned at the grid pixels only, not pre-zeroed) and
+               pre form (downstream outputs against a reference from the kernel's own gx)
+
+Every bf16 / fp32 output is an `Out` (sentinel NaN inside guards), every bits / argmax output a
+`ByteOut`; accumulators start nonzero.  Each case runs twice:
+
+  exact  small sparse integers (activations / gradients in {-1, 0, 1}, weights in {-2..2},
+         scales in {0.5, 1, 2}, integer shifts): every product sum is an integer far below 2^24,
+         so fp32 accumulation is exact in any order and across any atomics; bf16 outputs must be
+         bit-identical to the rounded fp64 reference and fp32 sums equal to it.  Outputs that are
+         summed afterwards are integers of magnitude <= 256 (bf16-exact).  The preconditions are
+         asserted on the reference alone.
+  real   randn inputs, every element within
+           2^-8 |ref| + (K + 4) U (|a| (*) |b|) |scale|
+         (one bf16 rounding with slack for a double-rounding boundary + fp32 accumulation over
+         the reduction length K, `(*)` the same contraction over absolute values); fp32
+         accumulators without the first term and K = the number of reduced rows.
+
+ReLU bits equal pack_bits of the kernel's own stored output, byte for byte.  Inputs come from a
+host generator, so the references (and the exact-case preconditions) are the same on any device.
+"""
+import functools
+from types import SimpleNamespace as NS
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from kernel_checks import ByteOut, Out, U, dev, pack_bits, pool_bwd_ref, pool_ref, rel64, ulps
+
+pytestmark = pytest.mark.gpu
+
+BF, F32 = torch.bfloat16, torch.float32
+KINDS = ["exact", "real"]
+PRECOND = {}     # kernel -> (largest sum |a||b|, largest |ref| of an output that is summed afterwards)
+
+
+def N():
+    from pddl.ops.native import require_native
+    return require_native()
+
+
+# ------------------------------------------------------------------------------- inputs
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def tern(g, *shape, p=0.25):
+    """{-1, 0, 1}, nonzero with probability p."""
+    s = torch.randint(0, 2, shape, generator=g) * 2 - 1
+    return (s * (torch.rand(shape, generator=g) < p)).to(BF).to(dev)
+
+
+def ints(g, lo, hi, *shape, dtype=BF):
+    return torch.randint(lo, hi + 1, shape, generator=g).to(dtype).to(dev)
+
+
+def pick(g, vals, n):
+    return torch.tensor(vals, dtype=F32)[torch.randint(0, len(vals), (n,), generator=g)].to(dev)
+
+
+def randn(g, *shape, scale=1.0, dtype=BF):
+    return (torch.randn(shape, generator=g) * scale).to(dtype).to(dev)
+
+
+def bn(g, n, exact):
+    """Folded-BN scale / shift of n channels."""
+    if exact:
+        return pick(g, (0.5, 1.0, 2.0), n), ints(g, -3, 3, n, dtype=F32)
+    return (torch.rand(n, generator=g) + 0.5).to(dev), randn(g, n, scale=0.1, dtype=F32)
+
+
+# ------------------------------------------------------------------------------- checks
+def precond(kernel, mag, summed=None):
+    """Exact-case preconditions, on the reference alone: every sum of |a||b| below 2^24, and the
+    outputs that are summed afterwards integers of magnitude <= 256."""
+    m = float(mag.max())
+    assert m < 2 ** 24, f"{kernel}: test bug, sum |a||b| = {m}"
+    r = 0.0
+    if summed is not None:
+        r = float(summed.abs().max())
+        assert r <= 256 and bool((summed == summed.round()).all()), f"{kernel}: test bug, |ref| = {r}"
+    old = PRECOND.get(kernel, (0.0, 0.0))
+    PRECOND[kernel] = (max(old[0], m), max(old[1], r))
+
+
+def check_exact(got, ref64, what):
+    """bf16: bit-identical to the rounded fp64 reference (which is an exact fp32 value, so its
+    conversion rounds once; the sign of a zero aside).  fp32 and folded (fp64) sums: equal."""
+    got, ref64 = got.reshape(-1), ref64.reshape(-1)
+    if got.dtype == BF:
+        bad = ulps(got, ref64.to(BF)) != 0
+    else:
+        bad = got.double() != ref64
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ, the first at flat index {i}: "
+                             f"{got[i].item()} for {ref64[i].item()} (norm-relative {rel64(got, ref64):.2e})")
+
+
+def check_real(got, ref64, mag, K, what, rounded=True):
+    """|got - ref| <= 2^-8 |ref| + (K + 4) U mag per element (`rounded`: a bf16 output)."""
+    got, ref64, mag = got.double().reshape(-1), ref64.reshape(-1), mag.reshape(-1)
+    bound = (K + 4) * U * mag + (2.0 ** -8 * ref64.abs() if rounded else 0.0)
+    err = (got - ref64).abs()
+    over = ~(err <= bound)
+    worst = float((err / bound.clamp_min(1e-300)).nan_to_num(posinf=float("inf")).max())
+    print(f"{what}: worst err / bound {worst:.3f}")
+    if bool(over.any()):
+        i = int(torch.where(over, err - bound, -1.0).nan_to_num(nan=float("inf")).argmax())
+        raise AssertionError(f"{what}: {int(over.sum())} of {over.numel()} elements over the bound, the worst at flat "
+                             f"index {i}: {got[i].item()} for {ref64[i].item()}, |err| {err[i].item():.3e} > "
+                             f"{bound[i].item():.3e}")
+
+
+def check(kind, got, ref64, mag, K, what, rounded=True):
+    if kind == "exact":
+        check_exact(got, ref64, what)
+    else:
+        check_real(got, ref64, mag, K, what, rounded)
+
+
+def check_bits(bt, out, what):
+    bt.check(what)
+    assert torch.equal(bt.t, pack_bits(out.t)), f"{what}: bits != packed (stored output > 0)"
+
+
+def untouched(bt, what):
+    bt.check(what)
+    assert bool((bt.t == 0xA5).all()), f"{what}: bits written without a bits buffer"
+
+
+def nothing(n):
+    return torch.zeros(n, dtype=torch.bool, device=dev)
+
+
+# --------------------------------------------------------------------------- conv3x3c64
+C64_SHAPES = [(1, 1, 1), (2, 3, 62), (3, 5, 7), (2, 9, 61), (5, 4, 16)]      # (N, H, W)
+
+
+def conv64(x, w):
+    """3x3 / pad 1 / stride 1, 64 -> 64, fp64: x [N, H, W, 64], w [64, 576] with k = (r * 3 + s) * 64 + ci."""
+    n, h, wd, _ = x.shape
+    xp = F.pad(x.double(), (0, 0, 1, 1, 1, 1))
+    wt = w.double().view(64, 9, 64)
+    out = torch.zeros(n, h, wd, 64, dtype=torch.float64, device=x.device)
+    for r in range(3):
+        for s in range(3):
+            out += xp[:, r:r + h, s:s + wd] @ wt[:, r * 3 + s].t()
+    return out
+
+
+def wgrad64(x, gy):
+    """dW[co][(r * 3 + s) * 64 + ci] = sum over pixels of gy[pixel][co] x[pixel + (r - 1, s - 1)][ci], fp64."""
+    n, h, wd, _ = x.shape
+    xp = F.pad(x.double(), (0, 0, 1, 1, 1, 1))
+    g2 = gy.double().reshape(-1, 64)
+    dw = torch.zeros(64, 9, 64, dtype=torch.float64, device=x.device)
+    for r in range(3):
+        for s in range(3):
+            dw[:, r * 3 + s] = g2.t() @ xp[:, r:r + h, s:s + wd].reshape(-1, 64)
+    return dw.view(64, 576)
+
+
+@functools.lru_cache(maxsize=None)
+def c64_case(shape, kind):
+    n, h, w = shape
+    exact = kind == "exact"
+    g = gen(1000 + 64 * h + w + exact)
+    if exact:
+        x, gy, wt = tern(g, n, h, w, 64), tern(g, n, h, w, 64), ints(g, -2, 2, 64, 576)
+    else:
+        x, gy, wt = randn(g, n, h, w, 64), randn(g, n, h, w, 64), randn(g, 64, 576, scale=0.05)
+    sc, sh = bn(g, 64, exact)
+    keep = randn(g, n, h, w, 64)                  # the data gradient's ReLU mask: bits of (keep > 0)
+    conv, mag = conv64(x, wt), conv64(x.abs(), wt.abs())
+    c = NS(x=x, gy=gy, w=wt, sc=sc, sh=sh, mbits=pack_bits(keep).view(n, h, w, 8))
+    c.fwd, c.fwd_mag = torch.relu(conv * sc.double() + sh.double()), mag * sc.double().abs() + sh.double().abs()
+    c.dg, c.dg_mag = conv * (keep.double() > 0), mag * (keep.double() > 0)
+    c.dw, c.dw_mag = wgrad64(x, gy), wgrad64(x.abs(), gy.abs())
+    if exact:
+        precond("conv3x3c64", mag, c.dg)
+        precond("conv3x3c64_wgrad", c.dw_mag)
+    return c
+
+
+@pytest.fixture
+def knob():
+    nat, used = N(), []
+
+    def set_(which, v):
+        used.append(which)
+        nat.set_variant(which, v)
+    try:
+        yield set_
+    finally:
+        for which in used:
+            nat.set_variant(which, 0)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("grid", [0, 1, 3])
+@pytest.mark.parametrize("shape", C64_SHAPES, ids=str)
+def test_conv3x3c64_forward(knob, shape, grid, kind):
+    nat, (n, h, w), c = N(), shape, c64_case(shape, kind)
+    M = n * h * w
+    knob("c64_grid", grid)
+    for with_bits in (True, False):
+        what = f"conv3x3c64 fwd {shape} grid={grid} {kind} bits={with_bits}"
+        out, bt = Out(M * 64, BF), ByteOut(M * 8)
+        nat.conv3x3c64(c.x, c.w, 0, out.t.view(n, h, w, 64), scale=c.sc, shift=c.sh,
+                       bits=bt.t.view(n, h, w, 8) if with_bits else None)
+        out.check(what)
+        check(kind, out.t, c.fwd, c.fwd_mag, 576, what)
+        if with_bits:
+            check_bits(bt, out, what)
+        else:
+            untouched(bt, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("grid", [0, 1, 3])
+@pytest.mark.parametrize("shape", C64_SHAPES, ids=str)
+def test_conv3x3c64_dgrad(knob, shape, grid, kind):
+    """The masked data gradient and its partial column sums: 4 rows per workgroup, summed in fp32
+    before the bf16 rounding (so M more additions per channel in the real case), the rows of the
+    workgroups the grid leaves out zero."""
+    nat, (n, h, w), c = N(), shape, c64_case(shape, kind)
+    M = n * h * w
+    rows = nat.conv3x3c64_partial_rows(M)
+    knob("c64_grid", grid)
+    what = f"conv3x3c64 dgrad {shape} grid={grid} {kind}"
+    out, part = Out(M * 64, BF), Out(rows * 64, F32)
+    nat.conv3x3c64(c.x, c.w, 1, out.t.view(n, h, w, 64), bits=c.mbits, colsum=part.t)
+    out.check(what)
+    part.check(what + " colsum")
+    check(kind, out.t, c.dg, c.dg_mag, 576, what)
+    used = min(n * ((h + 3) // 4), grid if grid else rows // 4, rows // 4)
+    assert bool((part.t.view(rows, 64)[4 * used:] == 0).all()), f"{what}: rows of idle workgroups not zero"
+    check(kind, part.t.view(rows, 64).double().sum(0), c.dg.sum((0, 1, 2)), c.dg_mag.sum((0, 1, 2)), 576 + M + 2,
+          what + " colsum", rounded=False)
+
+
+def test_conv3x3c64_rejects_w63():
+    nat = N()
+    g = gen(63)
+    x, wt = tern(g, 1, 2, 63, 64), ints(g, -2, 2, 64, 576)
+    sc, sh = bn(g, 64, True)
+    M = 2 * 63
+    out, bt, dw = Out(M * 64, BF), ByteOut(M * 8), Out(64 * 576, F32)
+    with pytest.raises(RuntimeError, match="62"):
+        nat.conv3x3c64(x, wt, 0, out.t.view(1, 2, 63, 64), scale=sc, shift=sh, bits=bt.t.view(1, 2, 63, 8))
+    with pytest.raises(RuntimeError, match="62"):
+        nat.conv3x3c64_wgrad(x, x, dw.t.view(64, 576))
+    torch.cuda.synchronize()
+    out.check("conv3x3c64 W=63", nothing(M * 64))
+    dw.check("conv3x3c64_wgrad W=63", nothing(64 * 576))
+    untouched(bt, "conv3x3c64 W=63")
+
+
+C64W_CASES = [(s, g_, 576) for s in C64_SHAPES for g_ in (0, 1, 2)] + [((3, 5, 7), 1, 640)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape,grid,ld", C64W_CASES, ids=str)
+def test_conv3x3c64_wgrad(knob, shape, grid, ld, kind):
+    nat, (n, h, w), c = N(), shape, c64_case(shape, kind)
+    what = f"conv3x3c64_wgrad {shape} grid={grid} ld_dw={ld} {kind}"
+    if ld == 576:
+        dw, owned = Out(64 * ld, F32, start=torch.full((64 * ld,), 0.5, device=dev)), None
+    else:       # the 64 pad columns of each row are not the kernel's: they stay sentinel
+        dw = Out(64 * ld, F32)
+        dw.t.view(64, ld)[:, :576] = 0.5
+        owned = (torch.arange(64 * ld, device=dev) % ld) < 576
+    knob("c64w_grid", grid)
+    nat.conv3x3c64_wgrad(c.x, c.gy, dw.t.view(64, ld))
+    dw.check(what, owned)
+    check(kind, dw.t.view(64, ld)[:, :576], c.dw + 0.5, c.dw_mag + 0.5, n * h * w, what, rounded=False)
+
+
+# --------------------------------------------------------------------------------- c3c1
+@functools.lru_cache(maxsize=None)
+def c3c1_case(M, kind):
+    exact = kind == "exact"
+    g = gen(2000 + 2 * M + exact)
+    sc3, sh3 = bn(g, 256, exact)
+    sc1, sh1 = bn(g, 64, exact)
+    if exact:
+        a, w3, w1 = tern(g, M, 64), ints(g, -2, 2, 256, 64), ints(g, -2, 2, 64, 256)
+        w3 = (w3.float() * torch.where(sc3 == 0.5, 2.0, 1.0).view(256, 1)).to(BF)    # the block output stays an integer
+        res = ints(g, 0, 3, M, 256)
+    else:
+        a, w3, w1 = torch.relu(randn(g, M, 64)), randn(g, 256, 64, scale=0.05), randn(g, 64, 256, scale=0.05)
+        res = torch.relu(randn(g, M, 256))
+    acc, mag = a.double() @ w3.double().t(), a.double().abs() @ w3.double().abs().t()
+    c = NS(a=a, w3=w3, sc3=sc3, sh3=sh3, w1=w1, sc1=sc1, sh1=sh1, res=res)
+    pre, c.mag = acc * sc3.double() + sh3.double(), mag * sc3.double().abs() + sh3.double().abs()
+    c.out = {False: torch.relu(pre), True: torch.relu(pre + res.double())}
+    c.out_mag = {False: c.mag, True: c.mag + res.double().abs()}
+    if exact:
+        precond("c3c1", mag, torch.cat([c.out[False], c.out[True]]))
+    return c
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("with_bits", [True, False])
+@pytest.mark.parametrize("with_res", [True, False])
+@pytest.mark.parametrize("M", [1, 63, 64, 65, 200])
+def test_c3c1(M, with_res, with_bits, kind):
+    nat, c = N(), c3c1_case(M, kind)
+    what = f"c3c1 M={M} res={with_res} bits={with_bits} {kind}"
+    out, y1, b3, b1 = Out(M * 256, BF), Out(M * 64, BF), ByteOut(M * 32), ByteOut(M * 8)
+    nat.c3c1(c.a, c.w3, c.sc3, c.sh3, c.res if with_res else None, out.t.view(M, 256), b3.t if with_bits else None,
+             c.w1, c.sc1, c.sh1, y1.t.view(M, 64), b1.t if with_bits else None)
+    out.check(what + " out")
+    y1.check(what + " y1")
+    check(kind, out.t, c.out[with_res], c.out_mag[with_res], 64, what + " out")
+    # phase 2 reads the rounded block output: its reference starts from the kernel's own `out`
+    o = out.t.view(M, 256).double()
+    mag1 = o.abs() @ c.w1.double().abs().t()
+    if kind == "exact":
+        precond("c3c1 y1", mag1)
+    check(kind, y1.t, torch.relu(o @ c.w1.double().t() * c.sc1.double() + c.sh1.double()),
+          mag1 * c.sc1.double().abs() + c.sh1.double().abs(), 256, what + " y1")
+    if with_bits:
+        check_bits(b3, out, what + " bits3")
+        check_bits(b1, y1, what + " bits1")
+    else:
+        untouched(b3, what + " bits3")
+        untouched(b1, what + " bits1")
+
+
+# ------------------------------------------------------------------------- fused stem
+def stem_dims(crop):
+    hs = (crop + 6) // 2
+    return hs, hs - 3, (hs - 3) // 2
+
+
+def stem_cols(x2):
+    """The 4x4 / stride-1 window of the space-to-depth input as GEMM rows, fp64:
+    [B, Hs, Ws, 16] -> [B, H1, W1, 256], k = (R * 4 + S) * 16 + c."""
+    B, Hs, Ws, _ = x2.shape
+    xw = x2.double().unfold(1, 4, 1).unfold(2, 4, 1)            # [B, H1, W1, 16, R, S]
+    return xw.permute(0, 1, 2, 4, 5, 3).reshape(B, Hs - 3, Ws - 3, 256)
+
+
+def at_tap(v, tap):
+    """v [B, H1, W1, C] at the window tap of every pool output (0 where the tap is padding)."""
+    B, _, _, C = v.shape
+    Ho, Wo = tap.shape[1:3]
+    vp = F.pad(v, (0, 0, 1, 1, 1, 1))
+    ar = lambda n_, *s: torch.arange(n_, device=v.device).view(*s)
+    t = tap.long()
+    return vp[ar(B, B, 1, 1, 1), 2 * ar(Ho, 1, Ho, 1, 1) + t // 3, 2 * ar(Wo, 1, 1, Wo, 1) + t % 3, ar(C, 1, 1, 1, C)]
+
+
+@functools.lru_cache(maxsize=None)
+def stem_fwd_case(B, crop, kind):
+    exact = kind == "exact"
+    hs, h1, h2 = stem_dims(crop)
+    g = gen(3000 + 4 * crop + 2 * B + exact)
+    if exact:
+        x2, w = tern(g, B, hs, hs, 16), ints(g, -2, 2, 64, 256)
+    else:
+        x2, w = randn(g, B, hs, hs, 16), randn(g, 64, 256, scale=0.08)
+    sc, sh = bn(g, 64, exact)
+    cols = stem_cols(x2)
+    mag = cols.abs() @ w.double().abs().t()
+    c = NS(x2=x2, w=w, sc=sc, sh=sh)
+    c.c1 = torch.relu(cols @ w.double().t() * sc.double() + sh.double())       # fp64, unrounded
+    # element bound of a stored conv value: (K + 4) U mag |scale| (+ |shift|) + one bf16 rounding
+    c.c1_bound = 2.0 ** -8 * c.c1 + (256 + 4) * U * (mag * sc.double().abs() + sh.double().abs())
+    if exact:
+        precond("stem_pool_fwd", mag)
+        c.best, c.tap = pool_ref(c.c1.to(BF))
+    else:
+        c.best, c.tap = pool_ref(c.c1)
+    return c
+
+
+STEM_CASES = [(B, crop, rows) for crop in (8, 28, 36) for B in (1, 3) for rows in (0, 1, 2, "all")] + [(1, 248, 0)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("B,crop,rows", STEM_CASES, ids=str)
+def test_stem_pool_fwd(B, crop, rows, kind):
+    """exact: the pool of the bf16-rounded conv rows bit for bit, the first maximum in scan order
+    (ReLU leaves many tied zeros).  real: with ĉ the kernel's conv values, |ĉ - c| <= b, the
+    kernel's tap t holds the largest ĉ, so its stored value is within b_t of c_t and the true
+    maximum c_s exceeds c_t by at most b_t + b_s."""
+    nat, c = N(), stem_fwd_case(B, crop, kind)
+    _, _, h2 = stem_dims(crop)
+    rows = h2 if rows == "all" else rows
+    n = B * h2 * h2 * 64
+    for with_bits in (True, False):
+        what = f"stem_pool_fwd B={B} crop={crop} rows={rows} {kind} bits={with_bits}"
+        pool, idx, bt = Out(n, BF), ByteOut(n), ByteOut(n // 8)
+        nat.stem_pool_fwd(c.x2, c.w, c.sc, c.sh, pool.t.view(B, h2, h2, 64), idx.t.view(B, h2, h2, 64),
+                          bt.t.view(B, h2, h2, 8) if with_bits else None, rows)
+        pool.check(what)
+        idx.check(what + " idx")
+        got, tap = pool.t.view(B, h2, h2, 64), idx.t.view(B, h2, h2, 64)
+        assert int(tap.max()) <= 8, f"{what}: an argmax tap was not written"
+        if kind == "exact":
+            check_exact(got, c.best, what)
+            assert torch.equal(tap, c.tap), f"{what}: tap is not the first maximum in scan order"
+        else:
+            c_t, b_t, b_s = at_tap(c.c1, tap), at_tap(c.c1_bound, tap), at_tap(c.c1_bound, c.tap)
+            err = (got.double() - c_t).abs()
+            assert bool((err <= b_t).all()), \
+                f"{what}: pool value {(err / b_t.clamp_min(1e-300)).max().item():.2f} x the bound"
+            short = c.best - c_t
+            assert bool((short <= b_t + b_s).all()), \
+                f"{what}: a tap is {(short / (b_t + b_s).clamp_min(1e-300)).max().item():.2f} x the bound below the maximum"
+        if with_bits:
+            check_bits(bt, pool, what)
+        else:
+            untouched(bt, what)
+
+
+def test_stem_pool_rejects_crop_252():
+    nat = N()
+    hs, _, h2 = stem_dims(252)
+    g = gen(252)
+    x2, w = tern(g, 1, hs, hs, 16), ints(g, -2, 2, 64, 256)
+    sc, sh = bn(g, 64, True)
+    n = h2 * h2 * 64
+    pool, idx, bt = Out(n, BF), ByteOut(n), ByteOut(n // 8)
+    with pytest.raises(RuntimeError, match="crop"):
+        nat.stem_pool_fwd(x2, w, sc, sh, pool.t.view(1, h2, h2, 64), idx.t.view(1, h2, h2, 64), bt.t.view(1, h2, h2, 8), 0)
+    dw, cs = Out(64 * 256, F32), Out(nat.stem_pool_bwd_partial_rows(1, h2, 0) * 64, F32)
+    with pytest.raises(RuntimeError, match="crop"):
+        nat.stem_pool_bwd(x2, tern(g, 1, h2, h2, 64), ints(g, 0, 8, 1, h2, h2, 64, dtype=torch.uint8), dw.t.view(64, 256),
+                          cs.t, 0)
+    torch.cuda.synchronize()
+    pool.check("stem_pool_fwd crop 252", nothing(n))
+    dw.check("stem_pool_bwd crop 252", nothing(64 * 256))
+    cs.check("stem_pool_bwd crop 252", nothing(cs.n))
+    untouched(idx, "stem_pool_fwd crop 252 idx")
+    untouched(bt, "stem_pool_fwd crop 252")
+
+
+@functools.lru_cache(maxsize=None)
+def stem_bwd_case(B, crop, kind):
+    exact = kind == "exact"
+    hs, h1, h2 = stem_dims(crop)
+    g = gen(4000 + 4 * crop + 2 * B + exact)
+    # taps of a real pool over integers with many negatives: ties, and zero pad taps that win
+    _, tap = pool_ref(ints(g, -3, 2, B, h1, h1, 64))
+    if exact:
+        x2, gpool, dw0 = tern(g, B, hs, hs, 16), ints(g, -3, 3, B, h2, h2, 64), ints(g, -9, 9, 64, 256, dtype=F32) + 0.5
+    else:
+        x2, gpool, dw0 = randn(g, B, hs, hs, 16), randn(g, B, h2, h2, 64), randn(g, 64, 256, dtype=F32)
+    cols = stem_cols(x2).reshape(-1, 256)
+    gc1 = pool_bwd_ref(gpool, tap, None, h1, h1)                     # conv1's output gradient, fp64
+    gabs = pool_bwd_ref(gpool.abs(), tap, None, h1, h1)
+    many = pool_bwd_ref(torch.ones_like(gpool), tap, None, h1, h1) >= 2
+    c = NS(x2=x2, gpool=gpool, tap=tap, dw0=dw0, gc1=gc1, gabs=gabs)
+    c.dw = dw0.double() + gc1.reshape(-1, 64).t() @ cols
+    c.dw_mag = dw0.double().abs() + gabs.reshape(-1, 64).t() @ cols.abs()
+    # a conv pixel fed by two to four pool outputs is their fp32 sum rounded to bf16 (as the unfused
+    # pair stores it) before the weight-gradient MFMAs: one more rounding of those pixels
+    c.dw_round = 2.0 ** -8 * (gabs * many).reshape(-1, 64).t() @ cols.abs()
+    if exact:
+        precond("stem_pool_bwd", c.dw_mag, gc1)
+        assert bool(((tap == 0) | (tap == 3)).any()) and bool((tap == 8).any())
+    return c
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("B,crop,rows", STEM_CASES, ids=str)
+def test_stem_pool_bwd(B, crop, rows, kind):
+    nat, c = N(), stem_bwd_case(B, crop, kind)
+    _, h1, h2 = stem_dims(crop)
+    rows = h2 if rows == "all" else rows
+    what = f"stem_pool_bwd B={B} crop={crop} rows={rows} {kind}"
+    prow = nat.stem_pool_bwd_partial_rows(B, h2, rows)
+    dw, cs = Out(64 * 256, F32, start=c.dw0), Out(prow * 64, F32)
+    nat.stem_pool_bwd(c.x2, c.gpool, c.tap, dw.t.view(64, 256), cs.t, rows)
+    dw.check(what + " dw")
+    cs.check(what + " colsum")
+    fold = cs.t.view(prow, 64).double().sum(0)
+    if kind == "exact":
+        check_exact(dw.t, c.dw, what + " dw")
+        check_exact(fold, c.gc1.sum((0, 1, 2)), what + " colsum")
+    else:
+        P = B * h1 * h1
+        err, bound = (dw.t.view(64, 256).double() - c.dw).abs(), (P + 4) * U * c.dw_mag + c.dw_round
+        print(f"{what}: dw worst err / bound {(err / bound).max().item():.3f}")
+        assert bool((err <= bound).all()), f"{what}: dw {(err / bound).max().item():.2f} x the bound"
+        # fp32 sums of the routed gradients before their rounding: at most h1 * h1 additions a row
+        check_real(fold, c.gc1.sum((0, 1, 2)), c.gabs.sum((0, 1, 2)), h1 * h1, what + " colsum", rounded=False)
+
+
+# ------------------------------------------------------------------------------- bwd1x1
+def b1_inputs(g, M, CO, CI, exact, ld_wd=None):
+    ld_wd = ld_wd or CO
+    wd = torch.full((CI, ld_wd), float("inf"), dtype=BF, device=dev)          # pad columns are never read
+    if exact:
+        gy, x, dw0 = tern(g, M, CO), tern(g, M, CI), ints(g, -9, 9, CO, CI, dtype=F32) + 0.5
+        wd[:, :CO] = ints(g, -2, 2, CI, CO)
+    else:
+        gy, x, dw0 = randn(g, M, CO), torch.relu(randn(g, M, CI)), randn(g, CO, CI, dtype=F32)
+        wd[:, :CO] = randn(g, CI, CO, scale=0.05)
+    return gy, x, wd, dw0, randn(g, M, CI)      # the last: bits of (keep > 0) mask the data gradient
+
+
+def b1_refs(gy, x, wd, dw0, keep):
+    """out = bit * (g . Wd^T), dW = dW0 + g^T . x, each with its contraction over absolute values."""
+    CO = gy.shape[-1]
+    g2, x2, k2 = gy.double().reshape(-1, CO), x.double().reshape(-1, x.shape[-1]), keep.double().reshape(-1, x.shape[-1]) > 0
+    w = wd[:, :CO].double()
+    return NS(out=(g2 @ w.t()) * k2, out_mag=(g2.abs() @ w.abs().t()) * k2,
+              dw=dw0.double() + g2.t() @ x2, dw_mag=dw0.double().abs() + g2.abs().t() @ x2.abs())
+
+
+def b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what):
+    """The partial column sums (fp32, taken before the bf16 rounding: M more additions) and dW."""
+    fold = cs.t.view(rows, CI).double().sum(0)
+    check(kind, fold, r.out.sum(0), r.out_mag.sum(0), CO + M + 2, what + " colsum", rounded=False)
+    check(kind, dw.t.view(CO, ld_dw)[:, :CI], r.dw, r.dw_mag, M, what + " dw", rounded=False)
+
+
+B1_CASES = [(co, ci, M, False) for co, ci in ((256, 64), (512, 128)) for M in (1, 63, 64, 65, 257)] + \
+           [(256, 64, 65, True), (512, 128, 65, True)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("CO,CI,M,padded", B1_CASES, ids=str)
+def test_bwd1x1_plain(CO, CI, M, padded, kind):
+    nat = N()
+    exact = kind == "exact"
+    ld_wd, ld_dw = (CO + 8, CI + 4) if padded else (CO, CI)
+    what = f"bwd1x1 ({CO},{CI}) M={M} padded={padded} {kind}"
+    gy, x, wd, dw0, keep = b1_inputs(gen(5000 + CO + 2 * M + exact), M, CO, CI, exact, ld_wd)
+    r = b1_refs(gy, x, wd, dw0, keep)
+    if exact:
+        precond("bwd1x1", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
+    rows = nat.bwd1x1_partial_rows(M, CO, CI)
+    out, cs = Out(M * CI, BF), Out(rows * CI, F32)
+    if padded:      # the pad columns of each dw row are not the kernel's: they stay sentinel
+        dw = Out(CO * ld_dw, F32)
+        dw.t.view(CO, ld_dw)[:, :CI] = dw0
+    else:
+        dw = Out(CO * CI, F32, start=dw0)
+    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(M, CI // 8), out.t.view(M, CI), cs.t, dw.t.view(CO, ld_dw))
+    out.check(what + " out")
+    cs.check(what + " colsum")
+    dw.check(what + " dw", (torch.arange(CO * ld_dw, device=dev) % ld_dw) < CI)
+    check(kind, out.t, r.out, r.out_mag, CO, what + " out")
+    b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("B,Hf,Wf", [(1, 7, 5), (2, 13, 11), (1, 6, 8), (2, 12, 10)], ids=str)
+@pytest.mark.parametrize("CO,CI", [(256, 64), (512, 128)])
+def test_bwd1x1_stride2(CO, CI, B, Hf, Wf, kind):
+    """The gradient lives on the stride-2 grid; `out` is full resolution, starts as sentinels and
+    must be written at the grid pixels only; `out2` is the compact copy."""
+    nat = N()
+    exact = kind == "exact"
+    Hc, Wc = (Hf + 1) // 2, (Wf + 1) // 2
+    M = B * Hc * Wc
+    what = f"bwd1x1 stride-2 ({CO},{CI}) B={B} {Hf}x{Wf} {kind}"
+    g = gen(6000 + CO + 16 * Hf + B + exact)
+    gy, _, wd, dw0, _ = b1_inputs(g, M, CO, CI, exact)
+    gy = gy.view(B, Hc, Wc, CO)
+    x = tern(g, B, Hf, Wf, CI) if exact else torch.relu(randn(g, B, Hf, Wf, CI))
+    keep = randn(g, B, Hf, Wf, CI)
+    r = b1_refs(gy, x[:, ::2, ::2], wd, dw0, keep[:, ::2, ::2])
+    if exact:
+        precond("bwd1x1 stride-2", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
+    rows = nat.bwd1x1_partial_rows(M, CO, CI)
+    out, out2, cs, dw = Out(B * Hf * Wf * CI, BF), Out(M * CI, BF), Out(rows * CI, F32), Out(CO * CI, F32, start=dw0)
+    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(B, Hf, Wf, CI // 8), out.t.view(B, Hf, Wf, CI), cs.t, dw.t.view(CO, CI),
+               out2.t.view(B, Hc, Wc, CI))
+    on_grid = torch.zeros(B, Hf, Wf, CI, dtype=torch.bool, device=dev)
+    on_grid[:, ::2, ::2] = True
+    out.check(what + " out", on_grid.reshape(-1))
+    out2.check(what + " out2")
+    cs.check(what + " colsum")
+    dw.check(what + " dw")
+    check(kind, out.t.view(B, Hf, Wf, CI)[:, ::2, ::2].contiguous(), r.out, r.out_mag, CO, what + " out")
+    check(kind, out2.t, r.out, r.out_mag, CO, what + " out2")
+    b1_check_sums(kind, cs, rows, CI, dw, CI, r, M, CO, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("M", [1, 65, 300])
+def test_bwd1x1_pre(M, kind):
+    """gx = bit(gmask) * (g1 . w1d^T + g) with its column sums against fp64; then the plain
+    form's outputs against a reference that starts from the kernel's own (rounded) gx."""
+    nat = N()
+    exact = kind == "exact"
+    what = f"bwd1x1 pre M={M} {kind}"
+    g = gen(7000 + 2 * M + exact)
+    if exact:
+        g1, w1d, add = tern(g, M, 64, p=0.125), ints(g, -1, 1, 256, 64), ints(g, -2, 2, M, 256)
+    else:
+        g1, w1d, add = randn(g, M, 64), randn(g, 256, 64, scale=0.05), randn(g, M, 256)
+    ox = randn(g, M, 256)
+    _, x, wd, dw0, keep = b1_inputs(g, M, 256, 64, exact)
+    if exact:
+        wd = (wd.float() * (torch.rand(64, 256, generator=g) < 0.125).to(dev)).to(BF)   # keeps |out| <= 256
+    on = ox.double() > 0
+    gx_ref = (g1.double() @ w1d.double().t() + add.double()) * on
+    gx_mag = (g1.double().abs() @ w1d.double().abs().t() + add.double().abs()) * on
+    if exact:
+        precond("bwd1x1 pre gx", gx_mag, gx_ref)
+    rows = nat.bwd1x1_partial_rows(M, 256, 64)
+    gx, csx = Out(M * 256, BF), Out(rows * 256, F32)
+    out, cs, dw = Out(M * 64, BF), Out(rows * 64, F32), Out(256 * 64, F32, start=dw0)
+    nat.bwd1x1(add, x, wd, pack_bits(keep).view(M, 8), out.t.view(M, 64), cs.t, dw.t.view(256, 64),
+               g1=g1, w1d=w1d, gmask=pack_bits(ox).view(M, 32), gx=gx.t.view(M, 256), colsum_gx=csx.t)
+    for o, name in ((gx, "gx"), (csx, "colsum_gx"), (out, "out"), (cs, "colsum"), (dw, "dw")):
+        o.check(f"{what} {name}")
+    check(kind, gx.t, gx_ref, gx_mag, 64, what + " gx")
+    fold = csx.t.view(rows, 256).double().sum(0)
+    check(kind, fold, gx_ref.sum(0), gx_mag.sum(0), 64 + M + 2, what + " colsum_gx", rounded=False)
+    r = b1_refs(gx.t.view(M, 256), x, wd, dw0, keep)
+    if exact:
+        precond("bwd1x1 pre", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
+    check(kind, out.t, r.out, r.out_mag, 256, what + " out")
+    b1_check_sums(kind, cs, rows, 64, dw, 64, r, M, 256, what)
