@@ -987,6 +987,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     else if (which == "igemm_sk_elig") { TORCH_CHECK(v >= 1 && v <= 8, "igemm_sk_elig: 1-8"); pddl::g_igemm_sk_elig = v; }
     else if (which == "igemm_pk_all") pddl::g_igemm_pk_all = v;
     else if (which == "igemm_pk_dual") pddl::g_igemm_pk_dual = v;
+    else if (which == "igemm_pk_grid") { TORCH_CHECK(v >= 0, "igemm_pk_grid: 0 (off) or a workgroup cap"); pddl::g_igemm_pk_grid = v; }
     else if (which == "igemm_pk") { TORCH_CHECK(v == 0 || (v >= 2 && v <= 4), "igemm_pk: 0 or ring depth 2-4"); pddl::g_igemm_pk = v; }
     else if (which == "wgrad8_min_rows") { TORCH_CHECK(v >= 64, "wgrad8_min_rows"); pddl::g_wgrad8_min_rows = v; }
     else if (which == "stem") pddl::g_stem_variant = v;
@@ -1005,6 +1006,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   // (kernel tests: did the forced tiling really run?)
   m.def("wgrad_last_tiling", []() { return pddl::g_wgrad_last_tiling; });
+  // The kernel launches of the calling thread's last igemm call, one dict per launch (a round-split
+  // call: 8-phase head + 128x128 tail; a split-K call: slices + combine):
+  //   kernel  "tile256x64" / "tile128x128" (igemm_kernel), "igemm8" / "igemm8_stagger",
+  //           "ring" / "ring_dual" (igemm_pk_kernel), "combine256x64" / "combine128x128"
+  //   stages  LDS stages of igemm_kernel, 1 or 2 (0 for the other kernels)
+  //   gather  "direct" / "halo" / "dual"
+  //   pf, bnz 1 for the epilogue-prefetch / fused BN-backward-sums instantiation
+  //   slices  split-K slices (1: unsplit; the combine reports the slices it folds)
+  //   kt, nb  the ring instantiation's K / 64 and ring depth (0 elsewhere)
+  //   grid    workgroups launched
+  m.def("igemm_last_launch", []() {
+    static const char* const kernel[] = {"tile256x64", "tile128x128", "igemm8", "igemm8_stagger",
+                                         "ring", "ring_dual", "combine256x64", "combine128x128"};
+    static const char* const gather[] = {"direct", "halo", "dual"};
+    pddl::IgemmLaunchInfo rec[4];
+    const int n = pddl::igemm_last_launch(rec, 4);
+    py::list out;
+    for (int i = 0; i < n; ++i) {
+      py::dict d;
+      d["kernel"] = kernel[rec[i].family];
+      d["stages"] = rec[i].stages;
+      d["gather"] = gather[rec[i].gather];
+      d["pf"] = rec[i].pf;
+      d["bnz"] = rec[i].bnz;
+      d["slices"] = rec[i].slices;
+      d["kt"] = rec[i].kt;
+      d["nb"] = rec[i].nb;
+      d["grid"] = rec[i].grid;
+      out.append(d);
+    }
+    return out;
+  });
   // (train/graph.py: is the stream's current capture still empty?) (hip error, capture status, #deps)
   m.def("stream_capture_deps", [](int64_t stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

@@ -1182,7 +1182,9 @@ int g_igemm_deep = 2;      // depth the heuristic uses for K >= 256 (3-stage mea
 int g_igemm_pf = 1;        // epilogue-operand prefetch (PF variant) for 1x1 layers with a residual / add
 int g_igemm8 = 2;          // 8-phase 256x256 kernel (igemm8_kernel) for Nn >= 256, K >= 256, Nn < 4K:
                            // 0 off, 1 on, 2 on with the wave-row stagger (default: b1024 end to end
-                           // 18.82k -> 19.00k img/s; stagger beats 1 on every layer, kbench)
+                           // 18.82k -> 19.00k img/s; stagger beats 1 on every layer, kbench);
+                           // +16 (tests): whatever the grid -- igemm8_min_tiles is ignored and a
+                           // problem without a full round of tiles stays on the 8-phase kernel
 int g_igemm_ns1_kt = 1000; // single-stage tile for K <= 64 * this (default: every K).  b1024 end to
                            // end 2/4/8/16/36 -> 20.11k/20.42k/20.53k/20.76k/20.87k img/s: three
                            // resident single-buffer blocks per CU overlap each other's load and MFMA
@@ -1244,7 +1246,7 @@ static int igemm_config(int M, int Nn, int K) {
   // (widths that are not a multiple of 256 stay on the 128x128 tile: conv3_block1 c1 + shortcut,
   // Nn = 640, measured 680 us on 8-phase tiles vs 588 us on five 128-wide tiles)
   if (g_igemm8 && Nn >= g_igemm8_min_n && K >= 256 && Nn < 4 * K && Nn % 256 == 0 &&
-      (long)((M + 255) / 256) * ((Nn + 255) / 256) >= g_igemm8_min_tiles)
+      ((g_igemm8 & 16) || (long)((M + 255) / 256) * ((Nn + 255) / 256) >= g_igemm8_min_tiles))
     return 4;
   return 1;
 }
@@ -1337,7 +1339,10 @@ static IgemmPlan igemm_plan(int M, int Nn, int K, bool bnz = false) {
   // the tail's 4r 128x128 tiles fit one round (2 per CU) when 2r <= C: it then costs about one
   // 128x128 tile time instead of a whole 256x256 round; a bigger tail runs as a full round
   if (r == 0 || 2 * r > C) return pl;
-  if (F == 0) { pl.cfg = 1; return pl; }
+  if (F == 0) {   // (igemm8 + 16: the 8-phase kernel whatever the grid)
+    if (!(g_igemm8 & 16)) pl.cfg = 1;
+    return pl;
+  }
   const long full_m_tiles = (F * C) / nt;
   pl.split = (int)lmin((long)M, full_m_tiles * 256);
   return pl;
@@ -1364,6 +1369,20 @@ int igemm_partial_rows(int M, int Nn, int K, bool bnz) {
 
 static void igemm_launch_cfg(const IgemmParams& p, int cfg, hipStream_t stream);
 
+// The launches of this thread's last igemm_launch (igemm_last_launch; kernels.h).
+static thread_local IgemmLaunchInfo tl_last[4];
+static thread_local int tl_nlast = 0;
+static void igemm_note(int family, int kt, int nb, int stages, int gather, bool pf, bool bnz, int slices, long grid) {
+  if (tl_nlast < 4) tl_last[tl_nlast] = IgemmLaunchInfo{family, kt, nb, stages, gather, pf ? 1 : 0, bnz ? 1 : 0, slices, (int)grid};
+  ++tl_nlast;
+}
+int igemm_last_launch(IgemmLaunchInfo* out, int max) {
+  const int n = tl_nlast < 4 ? tl_nlast : 4;
+  for (int i = 0; i < n && i < max; ++i) out[i] = tl_last[i];
+  return n;
+}
+
+int g_igemm_pk_grid = 0;    // test cap on the ring kernels' workgroup count (0: off), like c64_grid
 // The dual-source (projection block conv3 + shortcut) forward on the persistent ring: the
 // fused c3 + c0 launches of the four projection blocks (K = 128 / 384 / 768 / 1536).  The
 // one-block-per-CU 8-phase tiles and the 2-stage 128x128 tiles both serialise each tile's
@@ -1382,6 +1401,7 @@ static bool igemm_pk_dual_launch(const IgemmParams& p, hipStream_t stream) {
   const long T = (long)((p.M - p.m_begin + 127) / 128) * ((p.Nn + 127) / 128);
   long G = (long)num_cus() * 2;
   if (G > T) G = T;
+  if (g_igemm_pk_grid > 0 && G > g_igemm_pk_grid) G = g_igemm_pk_grid;
 #define PKD_GO(KT_) hipLaunchKernelGGL((igemm_pk_kernel<KT_, 2, true, true, true>), dim3((unsigned)G), dim3(256), 0, stream, p)
   if (KT == 2) PKD_GO(2);
   else if (KT == 6) PKD_GO(6);
@@ -1389,6 +1409,7 @@ static bool igemm_pk_dual_launch(const IgemmParams& p, hipStream_t stream) {
   else if (KT == 24) PKD_GO(24);
   else return false;
 #undef PKD_GO
+  igemm_note(IGF_RING_DUAL, KT, 2, 0, AM_DUAL, false, false, 1, G);
   return true;
 }
 
@@ -1408,6 +1429,7 @@ static bool igemm_pk_launch(const IgemmParams& p, hipStream_t stream) {
   const int nb = g_igemm_pk;
   long G = (long)num_cus() * (nb == 2 ? 2 : 1);
   if (G > T) G = T;
+  if (g_igemm_pk_grid > 0 && G > g_igemm_pk_grid) G = g_igemm_pk_grid;
 #define PK_GO(KT_, NB_)                                                                                      \
   {                                                                                                          \
     if (p.mode == EPI_FWD) hipLaunchKernelGGL((igemm_pk_kernel<KT_, NB_, true, true>), dim3((unsigned)G), dim3(256), 0, stream, p); \
@@ -1422,11 +1444,13 @@ static bool igemm_pk_launch(const IgemmParams& p, hipStream_t stream) {
   if (KT == 1) PK_NB(1) else if (KT == 2) PK_NB(2) else if (KT == 4) PK_NB(4) else PK_NB(8)
 #undef PK_NB
 #undef PK_GO
+  igemm_note(IGF_RING, KT, nb == 2 || nb == 3 ? nb : 4, 0, AM_DIRECT, false, false, 1, G);
   return true;
 }
 
 const char* igemm_launch(const IgemmParams& p_in, hipStream_t stream) {
   const char* why = nullptr;
+  tl_nlast = 0;
   if (!igemm_check(p_in, &why)) return why;
   IgemmParams p = p_in;
   p.mg_howo = fdiv_magic(p.Ho * p.Wo);
@@ -1452,6 +1476,7 @@ const char* igemm_launch(const IgemmParams& p_in, hipStream_t stream) {
     igemm_launch_cfg(p, pl.cfg, stream);
     if (pl.cfg == 0) hipLaunchKernelGGL((igemm_splitk_reduce_kernel<256, 64>), dim3(tiles * 4), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((igemm_splitk_reduce_kernel<128, 128>), dim3(tiles * 4), dim3(256), 0, stream, p);
+    igemm_note(pl.cfg == 0 ? IGF_COMBINE_256x64 : IGF_COMBINE_128x128, 0, 0, 0, 0, false, false, pl.ks, tiles * 4);
   } else if (pl.split < p.M) {
     IgemmParams head = p, tail = p;
     head.M = pl.split;
@@ -1501,6 +1526,7 @@ static void igemm_launch_cfg(const IgemmParams& p, int cfg, hipStream_t stream) 
       else { if (am == AM_DIRECT) IG_SK(256, 64, 2, AM_DIRECT); else IG_SK(256, 64, 2, AM_HALO); }
     }
 #undef IG_SK
+    igemm_note(cfg == 1 ? IGF_TILE_128x128 : IGF_TILE_256x64, 0, 0, ns == 1 ? 1 : 2, am, false, false, p.ksplit, nwg);
     return;
   }
   const bool pf = g_igemm_pf && am == AM_DIRECT && cfg <= 1 &&
@@ -1514,16 +1540,18 @@ static void igemm_launch_cfg(const IgemmParams& p, int cfg, hipStream_t stream) 
       if (am == AM_DIRECT) IG_Z(128, 128, AM_DIRECT); else IG_Z(128, 128, AM_HALO);
     }
 #undef IG_Z
+    igemm_note(cfg == 0 ? IGF_TILE_256x64 : IGF_TILE_128x128, 0, 0, 1, am, false, true, 1, nwg);
   } else if (cfg == 4) {
 #define IG_8(AM_)                                                                                         \
   {                                                                                                       \
-    if (g_igemm8 == 2) hipLaunchKernelGGL((igemm8_kernel<AM_, true>), dim3(nwg), dim3(512), 0, stream, p); \
+    if ((g_igemm8 & 7) == 2) hipLaunchKernelGGL((igemm8_kernel<AM_, true>), dim3(nwg), dim3(512), 0, stream, p); \
     else hipLaunchKernelGGL((igemm8_kernel<AM_, false>), dim3(nwg), dim3(512), 0, stream, p);             \
   }
     if (am == AM_DIRECT) IG_8(AM_DIRECT)
     else if (am == AM_HALO) IG_8(AM_HALO)
     else IG_8(AM_DUAL)
 #undef IG_8
+    igemm_note((g_igemm8 & 7) == 2 ? IGF_8PHASE_STAGGER : IGF_8PHASE, 0, 0, 0, am, false, false, 1, nwg);
   } else if (pf) {
 #define IG_PF(BM_, BN_, NS_) \
   hipLaunchKernelGGL((igemm_kernel<BM_, BN_, NS_, AM_DIRECT, true>), dim3(nwg), dim3(256), 0, stream, p)
@@ -1533,10 +1561,13 @@ static void igemm_launch_cfg(const IgemmParams& p, int cfg, hipStream_t stream) 
       if (ns == 1) IG_PF(256, 64, 1); else IG_PF(256, 64, 2);
     }
 #undef IG_PF
+    igemm_note(cfg == 1 ? IGF_TILE_128x128 : IGF_TILE_256x64, 0, 0, ns == 1 ? 1 : 2, am, true, false, 1, nwg);
   } else if (cfg == 1) {
     if (ns == 1) IG_MODES(128, 128, 1) else IG_MODES(128, 128, 2)
+    igemm_note(IGF_TILE_128x128, 0, 0, ns == 1 ? 1 : 2, am, false, false, 1, nwg);
   } else {
     if (ns == 1) IG_MODES(256, 64, 1) else IG_MODES(256, 64, 2)
+    igemm_note(IGF_TILE_256x64, 0, 0, ns == 1 ? 1 : 2, am, false, false, 1, nwg);
   }
 #undef IG_MODES
 #undef IG_GO

@@ -54,7 +54,25 @@ int igemm_partial_rows(int M, int Nn, int K, bool bnz = false);   // rows of the
 void igemm_plan_query(int M, int Nn, int K, int* cfg, int* split, int* ksplit = nullptr);   // tile config;
                                                     // rows >= split: 128x128 tail; ksplit: K slices (split-K)
 long igemm_splitk_floats(int M, int Nn, int K);     // split-K workspace a problem wants (0: no split)
-extern int g_igemm8, g_igemm8_min_tiles, g_igemm8_min_n, g_igemm_ns1_kt, g_wgrad8, g_wgrad1;
+// What the calling thread's last igemm_launch launched, one record per kernel launch (tests: did
+// the forced kernel really run?).  A round-split or split-K call leaves two.
+enum IgemmFamily {
+  IGF_TILE_256x64 = 0, IGF_TILE_128x128 = 1,   // igemm_kernel
+  IGF_8PHASE = 2, IGF_8PHASE_STAGGER = 3,      // igemm8_kernel
+  IGF_RING = 4, IGF_RING_DUAL = 5,             // igemm_pk_kernel (kt, nb set)
+  IGF_COMBINE_256x64 = 6, IGF_COMBINE_128x128 = 7   // igemm_splitk_reduce_kernel
+};
+struct IgemmLaunchInfo {
+  int family;          // IgemmFamily
+  int kt, nb;          // ring: K / 64 and ring depth of the instantiation (else 0)
+  int stages;          // igemm_kernel: LDS stages 1 / 2 (else 0)
+  int gather;          // AM_DIRECT 0 / AM_HALO 1 / AM_DUAL 2
+  int pf, bnz;         // epilogue-operand prefetch / fused BN-backward sums instantiation
+  int slices;          // split-K slices (1: unsplit)
+  int grid;            // workgroups launched
+};
+int igemm_last_launch(IgemmLaunchInfo* out, int max);   // -> number of records (at most max copied)
+extern int g_igemm8, g_igemm8_min_tiles, g_igemm8_min_n, g_igemm_ns1_kt, g_wgrad8, g_wgrad1, g_igemm_pk_grid;
 int num_cus();   // compute units of the current device (cached)
 extern int g_wgrad_f32_wpc[2];
 extern int g_wgrad_last_tiling;   // what the last wgrad launch took: 128 / 64 = wgrad_kernel of that co width, 1256 / 1128 = wgrad8_kernel (tests)

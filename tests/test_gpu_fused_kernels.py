@@ -41,112 +41,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kernel_checks import ByteOut, Out, U, dev, pack_bits, pool_bwd_ref, pool_ref, rel64, ulps
+from kernel_checks import (BF, F32, ByteOut, Out, U, bn, check, check_bits, check_exact, check_real, dev, gen, ints,
+                           nothing, pack_bits, pool_bwd_ref, pool_ref, precond, randn, tern, untouched)
 
 pytestmark = pytest.mark.gpu
 
-BF, F32 = torch.bfloat16, torch.float32
 KINDS = ["exact", "real"]
-PRECOND = {}     # kernel -> (largest sum |a||b|, largest |ref| of an output that is summed afterwards)
 
 
 def N():
     from pddl.ops.native import require_native
     return require_native()
-
-
-# ------------------------------------------------------------------------------- inputs
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def tern(g, *shape, p=0.25):
-    """{-1, 0, 1}, nonzero with probability p."""
-    s = torch.randint(0, 2, shape, generator=g) * 2 - 1
-    return (s * (torch.rand(shape, generator=g) < p)).to(BF).to(dev)
-
-
-def ints(g, lo, hi, *shape, dtype=BF):
-    return torch.randint(lo, hi + 1, shape, generator=g).to(dtype).to(dev)
-
-
-def pick(g, vals, n):
-    return torch.tensor(vals, dtype=F32)[torch.randint(0, len(vals), (n,), generator=g)].to(dev)
-
-
-def randn(g, *shape, scale=1.0, dtype=BF):
-    return (torch.randn(shape, generator=g) * scale).to(dtype).to(dev)
-
-
-def bn(g, n, exact):
-    """Folded-BN scale / shift of n channels."""
-    if exact:
-        return pick(g, (0.5, 1.0, 2.0), n), ints(g, -3, 3, n, dtype=F32)
-    return (torch.rand(n, generator=g) + 0.5).to(dev), randn(g, n, scale=0.1, dtype=F32)
-
-
-# ------------------------------------------------------------------------------- checks
-def precond(kernel, mag, summed=None):
-    """Exact-case preconditions, on the reference alone: every sum of |a||b| below 2^24, and the
-    outputs that are summed afterwards integers of magnitude <= 256."""
-    m = float(mag.max())
-    assert m < 2 ** 24, f"{kernel}: test bug, sum |a||b| = {m}"
-    r = 0.0
-    if summed is not None:
-        r = float(summed.abs().max())
-        assert r <= 256 and bool((summed == summed.round()).all()), f"{kernel}: test bug, |ref| = {r}"
-    old = PRECOND.get(kernel, (0.0, 0.0))
-    PRECOND[kernel] = (max(old[0], m), max(old[1], r))
-
-
-def check_exact(got, ref64, what):
-    """bf16: bit-identical to the rounded fp64 reference (which is an exact fp32 value, so its
-    conversion rounds once; the sign of a zero aside).  fp32 and folded (fp64) sums: equal."""
-    got, ref64 = got.reshape(-1), ref64.reshape(-1)
-    if got.dtype == BF:
-        bad = ulps(got, ref64.to(BF)) != 0
-    else:
-        bad = got.double() != ref64
-    if bool(bad.any()):
-        i = int(bad.nonzero()[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ, the first at flat index {i}: "
-                             f"{got[i].item()} for {ref64[i].item()} (norm-relative {rel64(got, ref64):.2e})")
-
-
-def check_real(got, ref64, mag, K, what, rounded=True):
-    """|got - ref| <= 2^-8 |ref| + (K + 4) U mag per element (`rounded`: a bf16 output)."""
-    got, ref64, mag = got.double().reshape(-1), ref64.reshape(-1), mag.reshape(-1)
-    bound = (K + 4) * U * mag + (2.0 ** -8 * ref64.abs() if rounded else 0.0)
-    err = (got - ref64).abs()
-    over = ~(err <= bound)
-    worst = float((err / bound.clamp_min(1e-300)).nan_to_num(posinf=float("inf")).max())
-    print(f"{what}: worst err / bound {worst:.3f}")
-    if bool(over.any()):
-        i = int(torch.where(over, err - bound, -1.0).nan_to_num(nan=float("inf")).argmax())
-        raise AssertionError(f"{what}: {int(over.sum())} of {over.numel()} elements over the bound, the worst at flat "
-                             f"index {i}: {got[i].item()} for {ref64[i].item()}, |err| {err[i].item():.3e} > "
-                             f"{bound[i].item():.3e}")
-
-
-def check(kind, got, ref64, mag, K, what, rounded=True):
-    if kind == "exact":
-        check_exact(got, ref64, what)
-    else:
-        check_real(got, ref64, mag, K, what, rounded)
-
-
-def check_bits(bt, out, what):
-    bt.check(what)
-    assert torch.equal(bt.t, pack_bits(out.t)), f"{what}: bits != packed (stored output > 0)"
-
-
-def untouched(bt, what):
-    bt.check(what)
-    assert bool((bt.t == 0xA5).all()), f"{what}: bits written without a bits buffer"
-
-
-def nothing(n):
-    return torch.zeros(n, dtype=torch.bool, device=dev)
 
 
 # --------------------------------------------------------------------------- conv3x3c64

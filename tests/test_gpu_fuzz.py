@@ -3,7 +3,8 @@ hypothesis draws batch / spatial / channel / kernel / stride combinations (chann
 of 64 as the kernels require, odd spatial sizes like the 244 / 160 crops produce) and every
 draw is compared with an fp32 PyTorch reference of the same op.  Includes the residual and
 residual-gradient epilogues, so both prefetch variants are exercised (knob igemm_pf), and the
-8-phase 256x256 kernel is forced onto tiny problems (igemm8_min_tiles=1) on half the draws."""
+8-phase 256x256 kernel is forced onto tiny problems (knob igemm8 + 16: whatever the grid) on half
+the draws; a draw it takes (Nn a multiple of 256, K >= 256, Nn < 4 K) must report that it ran."""
 import pytest
 import torch
 
@@ -38,9 +39,24 @@ conv = st.tuples(
 
 
 def _k8(on):
-    N().set_variant("igemm8", 2 if on else 0)
-    N().set_variant("igemm8_min_tiles", 1 if on else 128)
+    N().set_variant("igemm8", 18 if on else 0)
     N().set_variant("igemm8_min_n", 256 if on else 512)
+    N().set_variant("igemm_splitk", 0)       # (a planned split, taken or not, keeps the 4-wave tiles)
+
+
+def _k8_default():
+    N().set_variant("igemm8", 2)
+    N().set_variant("igemm8_min_n", 512)
+    N().set_variant("igemm_splitk", 1)
+
+
+def _ran_k8(k8, Nn, K):
+    """The kernels of the last igemm call; with k8, an eligible problem took the 8-phase kernel."""
+    ran = [l["kernel"] for l in N().igemm_last_launch()]
+    if k8 and Nn % 256 == 0 and K >= 256 and Nn < 4 * K:
+        assert ran == ["igemm8_stagger"], ran
+    else:
+        assert "igemm8_stagger" not in ran and "igemm8" not in ran, ran
 
 
 @settings(max_examples=25, deadline=None, derandomize=True)
@@ -62,11 +78,10 @@ def test_igemm_forward_fuzz(case, with_res, pf, k8):
     try:
         N().igemm(x, None, h, h, r, r, s, pad, ho, ho, w.view(co, -1), 0, sc, sh, res, None, None, out, 1, None, 0,
                   0, 0, 0, 0, None, None)
+        _ran_k8(k8, co, r * r * c)
     finally:
         N().set_variant("igemm_pf", 1)
-        _k8(True)
-        N().set_variant("igemm8_min_tiles", 128)
-    N().set_variant("igemm8_min_n", 512)
+        _k8_default()
     ref = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), stride=s,
                                      padding=pad).permute(0, 2, 3, 1) * sc + sh
     if with_res:
@@ -95,11 +110,10 @@ def test_igemm_dgrad_and_wgrad_fuzz(case, pf, k8):
     try:
         N().igemm(g, None, ho, ho, r, r, 1, r - 1 - pad, ho, ho, wt.view(cin, -1), 1, None, None, None, mask, add,
                   out, 0, None, 0, 0, 1 if s == 2 else 0, h, h, None, None)
+        _ran_k8(k8, cin, r * r * co)
     finally:
         N().set_variant("igemm_pf", 1)
-        _k8(True)
-        N().set_variant("igemm8_min_tiles", 128)
-    N().set_variant("igemm8_min_n", 512)
+        _k8_default()
     ref = torch.nn.grad.conv2d_input((n, cin, h, h), w.float().permute(0, 3, 1, 2), g.float().permute(0, 3, 1, 2),
                                      stride=s, padding=pad)
     ref = (ref.permute(0, 2, 3, 1) + add.float()) * (mask.float() > 0)

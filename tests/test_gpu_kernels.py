@@ -175,7 +175,9 @@ def test_igemm_big_tile_matches(kind, knob, big):
     """The 8-phase 256x256 kernel (igemm8 1, with the wave-row stagger 2), the forced 2-stage
     pipeline (igemm 2) and the epilogue-operand prefetch on single-stage dgrads (igemm_pf 2)
     compute the same result (same k order) as the default 4-wave 128x128 tile, including the
-    fused epilogues and the per-wave column-sum rows."""
+    fused epilogues and the per-wave column-sum rows.  These problems have 1-3 tiles of 256x256, so
+    the 8-phase kernel is forced (knob + 16: whatever the grid) where the problem is one it takes
+    (Nn a multiple of 256, K >= 256); igemm_last_launch() tells that it ran."""
     torch.manual_seed(12)
     n, h, ho = 3, 14, 7
     if kind == "fwd3x3":
@@ -205,7 +207,7 @@ def test_igemm_big_tile_matches(kind, knob, big):
     N().set_variant("igemm8_min_n", 256)       # (tiny problems: let the 8-phase kernel take them)
     N().set_variant("igemm8", 0)                 # baseline: the 128x128 tile
     default = KNOB_DEFAULTS.get(knob, 0)
-    for kv in (0, big):
+    for kv in (0, big + 16 if knob == "igemm8" else big):
         N().set_variant(knob, kv)
         try:
             if kind == "fwd3x3":
@@ -240,6 +242,11 @@ def test_igemm_big_tile_matches(kind, knob, big):
                 N().igemm(g1, g0, ho, ho, 1, 1, 1, 0, ho, ho, wt, 1, None, None, None, mask, None, out, 0, None, 0, 0,
                           1, h, h, part, None)
                 outs.append(torch.cat([out.float().flatten(), _fold(part, rows, 256)]))
+            ran = [l["kernel"] for l in N().igemm_last_launch()]
+            if knob == "igemm8" and kv and kind in ("fwd3x3", "dgrad_up2_dual"):
+                assert ran == ["igemm8_stagger" if big == 2 else "igemm8"], ran
+            else:
+                assert "igemm8" not in ran and "igemm8_stagger" not in ran, ran
         finally:
             N().set_variant(knob, default)
     N().set_variant("igemm8_min_tiles", 128)
@@ -283,11 +290,13 @@ def test_igemm8_round_split_dgrad_colsum(stagger):
     (4, 14, 256, 256, 3, 1, 1),
     (5, 7, 512, 512, 3, 1, 1),
     (3, 15, 512, 1280, 1, 2, 0),
-    (2, 9, 2048, 384, 1, 1, 0),
+    (2, 9, 2048, 512, 1, 1, 0),
 ])
 def test_igemm8_forward_vs_fp32(case, stagger):
     """8-phase kernel against the fp32 conv reference on ResNet-50 stage-4/5 shapes (K up to
-    4608 = 72 K-tiles through the counted-vmcnt pipeline; M and N tails)."""
+    4608 = 72 K-tiles through the counted-vmcnt pipeline; M tails).  The grids are 1-15 tiles, so
+    the kernel is forced (knob + 16) and igemm_last_launch() tells that it ran.  (Widths that are
+    not a multiple of 256 never plan this kernel: the long-K 1x1 has Nn = 512.)"""
     torch.manual_seed(21)
     n, h, c, co, r, st, pad = case
     x = rnd(n, h, h, c)
@@ -299,11 +308,13 @@ def test_igemm8_forward_vs_fp32(case, stagger):
     out = torch.empty(n, ho, ho, co, dtype=torch.bfloat16, device=dev)
     N().set_variant("igemm8_min_tiles", 1)
     N().set_variant("igemm8_min_n", 256)
-    N().set_variant("igemm8", stagger)
+    N().set_variant("igemm8", 16 + stagger)
     try:
         for _ in range(3):       # repeated launches: a pipeline race would show up as a changing result
             N().igemm(x, None, h, h, r, r, st, pad, ho, ho, w.view(co, -1), 0, scale, shift, res, None, None, out, 1,
                       None, 0, 0, 0, 0, 0, None, None)
+            ran = [l["kernel"] for l in N().igemm_last_launch()]
+            assert ran == ["igemm8_stagger" if stagger == 2 else "igemm8"], ran
             ref = (conv_ref(x, w, st, pad) * scale + shift + res.float()).relu()
             assert rel(out, ref) < 1e-2
     finally:
@@ -986,16 +997,18 @@ def test_igemm_splitk_dense_head_f32():
 
 @pytest.mark.parametrize("nb", [2, 3, 4])
 @pytest.mark.parametrize("case", ["fwd_res_k64", "fwd_res_k256_s2", "fwd_nores_k128", "fwd_res_k512",
-                                  "dgrad_add_k64", "dgrad_bits_k256", "dgrad_add_k128_nn320"])
+                                  "dgrad_add_k64", "dgrad_bits_k256", "dgrad_add_k128_nn288"])
 def test_igemm_pk_matches(case, nb):
     """The persistent ring kernel (igemm_pk) computes exactly what the per-tile kernel does on
     the short-K 1x1 layers: forward with residual + ReLU-bit output, dgrad with residual-gradient
     add + ReLU bits + fused column sums; several tiles per workgroup (the ring crosses tile
-    boundaries), an M tail (rows % 128 != 0), a half-empty column tile (Nn = 320) and stride 2."""
+    boundaries), an M tail (rows % 128 != 0), a partial column tile (Nn = 288 = 2 x 128 + 32: a
+    width that plans the 128x128 form, which the ring needs; Nn = 320 goes to the 256x64 tile by
+    the igemm_n64 rule) and stride 2.  igemm_last_launch() tells which kernel each run took."""
     torch.manual_seed(31)
     n, h = 32, 55                                  # M = 96800 rows: 757 row tiles, ~3-9 tiles per workgroup
     K = int(case.split("_k")[1].split("_")[0])
-    Nn = 320 if "nn320" in case else 256
+    Nn = 288 if "nn288" in case else 256
     st = 2 if case.endswith("_s2") else 1
     hi = h * st
     if case.startswith("fwd"):
@@ -1027,6 +1040,8 @@ def test_igemm_pk_matches(case, nb):
                           0, 0, 0, part, None)
                 outs.append(torch.cat([out.float().flatten(), _fold(part, rows, Nn)]))
             torch.cuda.synchronize()
+            ran = [(l["kernel"], l["kt"], l["nb"]) for l in N().igemm_last_launch()]
+            assert ran == ([("ring", K // 64, nb)] if kv else [("tile128x128", 0, 0)]), ran
         finally:
             N().set_variant("igemm_pk", 2)
     N().set_variant("igemm_pk_all", 0)
