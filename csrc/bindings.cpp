@@ -745,16 +745,21 @@ void opt_hparams(Tensor hs, double b1, double b2, bool adam) {
   PCHECK(hs.is_cuda() && hs.scalar_type() == torch::kFloat32 && hs.numel() >= 3, "hparams: device float[>=3]");
   ok(pddl::opt_hparams_launch(f32p(hs), (float)b1, (float)b2, adam ? 1 : 0, cur_stream()), "opt_hparams");
 }
+// gn (optional, every optimizer): the device float[8] of grad_norm, already filled for this step.
+const float* gnp(const OptT& gn) {
+  PCHECK(!gn.has_value() || (gn->numel() >= 8 && gn->is_contiguous()), "gn is device float[>=8]");
+  return of32p(gn);
+}
 void adam(Tensor p, Tensor g, Tensor m, Tensor v, double lr_t, double b1, double b2, double eps, double gscale,
-          OptT hs) {
+          OptT hs, OptT gn) {
   ok(pddl::adam_launch(f32p(p), f32p(g), f32p(m), f32p(v), p.numel(), (float)lr_t, (float)b1, (float)b2, (float)eps,
-                       (float)gscale, of32p(hs), cur_stream()),
+                       (float)gscale, of32p(hs), gnp(gn), cur_stream()),
      "adam");
 }
 void sgd(Tensor p, Tensor g, Tensor mom, double lr, double momentum, double wd, bool nesterov, double gscale,
-         OptT hs) {
+         OptT hs, OptT gn) {
   ok(pddl::sgd_launch(f32p(p), f32p(g), f32p(mom), p.numel(), (float)lr, (float)momentum, (float)wd,
-                      nesterov ? 1 : 0, (float)gscale, of32p(hs), cur_stream()),
+                      nesterov ? 1 : 0, (float)gscale, of32p(hs), gnp(gn), cur_stream()),
      "sgd");
 }
 void opt_hparams_sched(Tensor hs, double b1, double b2, bool adam) {
@@ -781,7 +786,8 @@ int64_t lars_chunks(Tensor table_host, int64_t n, int64_t chunk) {
   return c;
 }
 void lars(Tensor p, Tensor g, Tensor mom, Tensor table, Tensor table_host, int64_t chunk, Tensor partials,
-          Tensor ratios, double lr, double momentum, double wd, double eta, double eps, double gscale, OptT hs) {
+          Tensor ratios, double lr, double momentum, double wd, double eta, double eps, double gscale, OptT hs,
+          OptT gn) {
   int64_t nseg;
   const pddl::LarsSeg* segs = lars_host_table(table_host, nseg);
   PCHECK(table.is_cuda() && table.scalar_type() == torch::kInt32 && table.is_contiguous() &&
@@ -799,8 +805,19 @@ void lars(Tensor p, Tensor g, Tensor mom, Tensor table, Tensor table_host, int64
   ok(pddl::lars_launch(f32p(p), f32p(g), f32p(mom), p.numel(), reinterpret_cast<const pddl::LarsSeg*>(table.data_ptr()),
                        segs, (int)nseg, (int)chunk, f32p(partials), partials.numel(), f32p(ratios), ratios.numel(),
                        (float)lr, (float)momentum, (float)wd, (float)eta, (float)eps, (float)gscale, of32p(hs),
-                       cur_stream()),
+                       gnp(gn), cur_stream()),
      "lars");
+}
+// Global norm of gscale * g into gn[0], the clip scale into gn[1], the skip flag into gn[2] (kernels.h).
+void grad_norm(Tensor g, double gscale, int64_t chunk, Tensor partials, Tensor gn) {
+  PCHECK(g.is_contiguous() && partials.is_contiguous() && gn.is_contiguous() && gn.numel() >= 8 &&
+             g.device() == partials.device() && g.device() == gn.device(),
+         "grad_norm: g, partials and gn float[>=8] contiguous, on one device");
+  PCHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0, "grad_norm: g 16-byte aligned");
+  PCHECK(chunk > 0 && chunk <= INT32_MAX, "grad_norm: chunk out of range");
+  ok(pddl::grad_norm_launch(f32p(g), g.numel(), (float)gscale, (int)chunk, f32p(partials), partials.numel(), f32p(gn),
+                            cur_stream()),
+     "grad_norm");
 }
 void scale_(Tensor x, double a) { ok(pddl::scale_launch(f32p(x), x.numel(), (float)a, cur_stream()), "scale"); }
 void cast_bf16(Tensor x, Tensor y) { ok(pddl::cast_bf16_launch(f32p(x), bfpm(y), x.numel(), cur_stream()), "cast"); }
@@ -1068,12 +1085,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_grad", &bn_grad, REL);
   m.def("synth", &synth, REL);
   m.def("opt_hparams", &opt_hparams, REL);
-  m.def("adam", &adam, REL);
-  m.def("sgd", &sgd, REL);
+  m.def("adam", &adam, REL, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr_t"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("gscale"), py::arg("hs"), py::arg("gn") = none);
+  m.def("sgd", &sgd, REL, py::arg("p"), py::arg("g"), py::arg("momentum"), py::arg("lr"), py::arg("mu"), py::arg("wd"),
+        py::arg("nesterov"), py::arg("gscale"), py::arg("hs"), py::arg("gn") = none);
   m.def("opt_hparams_sched", &opt_hparams_sched, REL);
   m.def("lars", &lars, REL, py::arg("p"), py::arg("g"), py::arg("momentum"), py::arg("table"), py::arg("table_host"),
         py::arg("chunk"), py::arg("partials"), py::arg("ratios"), py::arg("lr"), py::arg("mu"), py::arg("wd"),
-        py::arg("eta"), py::arg("eps"), py::arg("gscale"), py::arg("hs") = none);
+        py::arg("eta"), py::arg("eps"), py::arg("gscale"), py::arg("hs") = none, py::arg("gn") = none);
+  m.def("grad_norm", &grad_norm, REL, py::arg("g"), py::arg("gscale"), py::arg("chunk"), py::arg("partials"),
+        py::arg("gn"));
+  m.attr("GRAD_NORM_DEFAULT_CHUNK") = (int)pddl::kGradNormDefaultChunk;
   m.def("lars_chunks", &lars_chunks, REL);
   m.attr("LARS_DEFAULT_CHUNK") = (int)pddl::kLarsDefaultChunk;
   m.def("scale_", &scale_, REL);

@@ -392,11 +392,13 @@ const char* synth_launch(const int64_t* idx, int n, long per, int64_t seed, int 
 
 // ---- optimizers (optim.hip) ----
 // hs (nullable): device {t, lr, lr_t}; when given, the step size is read from hs[2].
+// gn (nullable): the device buffer of grad_norm_launch; when given, the update multiplies gn[1]
+// into the gradient scale and does nothing when gn[2] is set.
 const char* opt_hparams_launch(float* hs, float b1, float b2, int adam, hipStream_t s);
 const char* adam_launch(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2,
-                        float eps, float gscale, const float* hs, hipStream_t s);
+                        float eps, float gscale, const float* hs, const float* gn, hipStream_t s);
 const char* sgd_launch(float* p, const float* g, float* mom, long n, float lr, float momentum, float wd,
-                       int nesterov, float gscale, const float* hs, hipStream_t s);
+                       int nesterov, float gscale, const float* hs, const float* gn, hipStream_t s);
 // Scheduled step hyper-parameters: hs = {t, lr, lr_t, lr_sched, warmup_steps, total_steps, end_lr, -}.
 const char* opt_hparams_sched_launch(float* hs, float b1, float b2, int adam, hipStream_t s);
 // LARS.  One table entry per segment of the trainable prefix, ascending and disjoint; offsets and
@@ -411,7 +413,13 @@ long lars_check_table(const LarsSeg* segs, int nseg, long n, int chunk, const ch
 const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSeg* segs_dev, const LarsSeg* segs_host,
                         int nseg, int chunk, float* partials, long partials_floats, float* ratios, long ratios_floats,
                         float lr, float momentum, float wd, float eta, float eps, float gscale, const float* hs,
-                        hipStream_t s);
+                        const float* gn, hipStream_t s);
+// Global gradient norm for clipping and the non-finite skip.  Chunk b = floats [b chunk, (b + 1) chunk)
+// of g is summed by block b into partials[b]; one block folds them and updates
+// gn[8] = {norm, scale, skip, clip, skip_enabled, clipped steps, skipped steps, -} (slots 3, 4 host-written).
+constexpr int kGradNormDefaultChunk = 16384;
+const char* grad_norm_launch(const float* g, long n, float gscale, int chunk, float* partials, long partials_floats,
+                             float* gn, hipStream_t s);
 const char* adam_bf16_wire_launch(float* p, const uint16_t* g, float* m, float* v, uint16_t* snap, long n, float lr_t,
                                   float b1, float b2, float eps, hipStream_t s);
 const char* scale_launch(float* x, long n, float a, hipStream_t s);

@@ -26,8 +26,12 @@ __global__ void opt_hparams_kernel(float* hs, float b1, float b2, int adam) {
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n4, float lr_t, float b1, float b2, float eps, float gs,
-                            const float* __restrict__ hs) {
+                            const float* __restrict__ hs, const float* __restrict__ gn) {
   if (hs) lr_t = hs[2];
+  if (gn) {   // (see grad_clip_finalize_kernel)
+    if (gn[2] != 0.f) return;
+    gs *= gn[1];
+  }
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float4 pp = reinterpret_cast<float4*>(p)[i];
     const float4 gg = reinterpret_cast<const float4*>(g)[i];
@@ -79,8 +83,13 @@ __global__ void adam_bf16_wire_kernel(float* __restrict__ p, const uint16_t* __r
 }
 
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom, long n4,
-                           float lr, float mu, float wd, int nesterov, float gs, const float* __restrict__ hs) {
+                           float lr, float mu, float wd, int nesterov, float gs, const float* __restrict__ hs,
+                           const float* __restrict__ gn) {
   if (hs) lr = hs[2];
+  if (gn) {
+    if (gn[2] != 0.f) return;
+    gs *= gn[1];
+  }
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float4 pp = reinterpret_cast<float4*>(p)[i];
     const float4 gg = reinterpret_cast<const float4*>(g)[i];
@@ -154,8 +163,13 @@ __device__ __forceinline__ float2 lars_block_sum2(float a, float b, float2* red)
 
 __global__ __launch_bounds__(256) void lars_norm_kernel(const float* __restrict__ p, const float* __restrict__ g,
                                                         const LarsSeg* __restrict__ segs, int nseg, int chunk,
-                                                        float gs, float2* __restrict__ partials) {
+                                                        float gs, float2* __restrict__ partials,
+                                                        const float* __restrict__ gn) {
   __shared__ float2 red[4];
+  if (gn) {
+    if (gn[2] != 0.f) return;   // (skipped step: the update pass returns before it reads the partials)
+    gs *= gn[1];
+  }
   const int b = blockIdx.x;
   const LarsSeg sg = segs[lars_find_seg(segs, nseg, b)];
   if (!sg.adapt) return;   // (its partials are never read)
@@ -180,9 +194,14 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ p,
                                                           int nseg, int chunk, const float2* __restrict__ partials,
                                                           float* __restrict__ ratios, float lr, float mu, float wd,
                                                           float eta, float eps, float gs,
-                                                          const float* __restrict__ hs) {
+                                                          const float* __restrict__ hs,
+                                                          const float* __restrict__ gn) {
   __shared__ float2 red[4];
   if (hs) lr = hs[2];
+  if (gn) {
+    if (gn[2] != 0.f) return;   // (the ratios of the last applied step stay)
+    gs *= gn[1];
+  }
   const int b = blockIdx.x;
   const int s = lars_find_seg(segs, nseg, b);
   const LarsSeg sg = segs[s];
@@ -222,6 +241,58 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ p,
 #undef LARS1
     p4[i] = pp;
     v4[i] = vv;
+  }
+}
+
+// ---- global-norm gradient clipping and non-finite skip ------------------------------------
+// The whole-buffer form of the LARS norm pass, under the same rule (above lars_find_seg):
+// replicas clip identical all-reduced gradients and nothing re-synchronises the parameters
+// afterwards, so the norm comes out bit-identical everywhere.  Block b sums (gs g)^2 over floats
+// [b chunk, min(n, (b + 1) chunk)) in the fixed thread -> wave -> block tree and writes
+// partials[b]; one block then folds the partials (lane j takes j, j + 256, ... in index order,
+// then the same tree).  No atomics: the order is a pure function of (n, chunk), never of the
+// grid cap, the CU count or arrival order.
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* __restrict__ g, long n, int chunk, float gs,
+                                                         float* __restrict__ partials) {
+  __shared__ float2 red[4];
+  const long start = (long)blockIdx.x * chunk;
+  const int n4 = (int)lmin((long)chunk, n - start) >> 2;
+  const float4* g4 = reinterpret_cast<const float4*>(g + start);
+  float sgg = 0.f;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 d = g4[i];
+    d.x *= gs; d.y *= gs; d.z *= gs; d.w *= gs;
+    sgg += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+  }
+  const float2 r = lars_block_sum2(sgg, 0.f, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = r.x;
+}
+
+// gn = {norm, scale, skip, clip, skip_enabled, clipped steps, skipped steps, -}: slots 0..2 and
+// the two counters are written here, slots 3 and 4 by the host.  norm = sqrt(sum (gs g)^2) of
+// this step before clipping; scale = clip / norm when clip > 0 and norm > clip, else exactly
+// 1.0f (Keras: clip / max(norm, clip)), so gs * scale is bitwise gs on a step that is not
+// clipped; skip = 1 when skip_enabled and the norm is not finite.  The sum of squares is
+// non-finite exactly when some gs g is NaN or +-inf or the sum overflows fp32, so the norm is
+// also the non-finite detector.  The update kernels that are given gn multiply scale into gs
+// and return at once when skip is set: p, the slots and the LARS ratios stay bit-unchanged.
+// hs[0] still advances on a skipped step (the hparams kernel runs before this one), so the
+// host and device step counts never diverge.  A NaN norm compares false with clip: scale 1.
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const float* __restrict__ partials, int m,
+                                                                 float* __restrict__ gn) {
+  __shared__ float2 red[4];
+  float sgg = 0.f;
+  for (int j = threadIdx.x; j < m; j += 256) sgg += partials[j];
+  const float2 r = lars_block_sum2(sgg, 0.f, red);
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf(r.x), clip = gn[3];
+    const float scale = (clip > 0.f && norm > clip) ? clip / norm : 1.0f;
+    const bool skip = gn[4] != 0.f && !isfinite(norm);
+    gn[0] = norm;
+    gn[1] = scale;
+    gn[2] = skip ? 1.f : 0.f;
+    if (scale < 1.0f && !skip) gn[5] += 1.f;   // (a skipped step applies nothing, clipped or not)
+    if (skip) gn[6] += 1.f;
   }
 }
 
@@ -295,17 +366,17 @@ const char* opt_hparams_launch(float* hs, float b1, float b2, int adam, hipStrea
   LAUNCH_RET
 }
 const char* adam_launch(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2,
-                        float eps, float gscale, const float* hs, hipStream_t s) {
+                        float eps, float gscale, const float* hs, const float* gn, hipStream_t s) {
   if (n % 4) return "adam: n must be a multiple of 4";
   hipLaunchKernelGGL(adam_kernel, dim3(grid_of(n / 4)), dim3(256), 0, s, p, g, m, v, n / 4, lr_t, b1, b2, eps, gscale,
-                     hs);
+                     hs, gn);
   LAUNCH_RET
 }
 const char* sgd_launch(float* p, const float* g, float* mom, long n, float lr, float momentum, float wd, int nesterov,
-                       float gscale, const float* hs, hipStream_t s) {
+                       float gscale, const float* hs, const float* gn, hipStream_t s) {
   if (n % 4) return "sgd: n must be a multiple of 4";
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_of(n / 4)), dim3(256), 0, s, p, g, mom, n / 4, lr, momentum, wd, nesterov,
-                     gscale, hs);
+                     gscale, hs, gn);
   LAUNCH_RET
 }
 const char* opt_hparams_sched_launch(float* hs, float b1, float b2, int adam, hipStream_t s) {
@@ -336,16 +407,27 @@ long lars_check_table(const LarsSeg* segs, int nseg, long n, int chunk, const ch
 const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSeg* segs_dev, const LarsSeg* segs_host,
                         int nseg, int chunk, float* partials, long partials_floats, float* ratios, long ratios_floats,
                         float lr, float momentum, float wd, float eta, float eps, float gscale, const float* hs,
-                        hipStream_t s) {
+                        const float* gn, hipStream_t s) {
   const char* err;
   const long chunks = lars_check_table(segs_host, nseg, n, chunk, &err);
   if (chunks < 0) return err;
   if (partials_floats < 2 * chunks) return "lars: partials buffer smaller than 2 floats per chunk";
   if (ratios_floats < nseg) return "lars: ratio buffer smaller than the segment table";
   hipLaunchKernelGGL(lars_norm_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, segs_dev, nseg, chunk, gscale,
-                     reinterpret_cast<float2*>(partials));
+                     reinterpret_cast<float2*>(partials), gn);
   hipLaunchKernelGGL(lars_update_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, v, segs_dev, nseg, chunk,
-                     reinterpret_cast<const float2*>(partials), ratios, lr, momentum, wd, eta, eps, gscale, hs);
+                     reinterpret_cast<const float2*>(partials), ratios, lr, momentum, wd, eta, eps, gscale, hs, gn);
+  LAUNCH_RET
+}
+const char* grad_norm_launch(const float* g, long n, float gscale, int chunk, float* partials, long partials_floats,
+                             float* gn, hipStream_t s) {
+  if (n <= 0 || n % 4) return "grad_norm: n must be a positive multiple of 4";
+  if (chunk < 4 || chunk % 4) return "grad_norm: chunk must be a positive multiple of 4";
+  const long chunks = (n + (long)chunk - 1) / chunk;
+  if (chunks > 0x7fffffffL) return "grad_norm: too many chunks";
+  if (partials_floats < chunks) return "grad_norm: partials buffer smaller than one float per chunk";
+  hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)chunks), dim3(256), 0, s, g, n, chunk, gscale, partials);
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, s, partials, (int)chunks, gn);
   LAUNCH_RET
 }
 const char* scale_launch(float* x, long n, float a, hipStream_t s) {

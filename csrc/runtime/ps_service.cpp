@@ -240,7 +240,7 @@ class PSServer {
             "adam (bf16 wire)");
       else
         kck(pddl::adam_launch(params_, g, m_, v_, n_, (float)lr_t, (float)b1_, (float)b2_, (float)eps_, 1.f, nullptr,
-                              stream_),
+                              nullptr, stream_),
             "adam");
     } else {
       const float b1 = (float)b1_, b2 = (float)b2_, eps = (float)eps_, lt = (float)lr_t;

@@ -11,7 +11,7 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import check_accum, check_loss, config_from_args
+from .config import check_accum, check_clip, check_loss, config_from_args
 
 
 def _banner(cfg, strategy):
@@ -21,7 +21,8 @@ def _banner(cfg, strategy):
           f"per-replica batch={strategy.per_replica_batch}, global batch={strategy.global_batch}, "
           f"accum_steps={cfg.accum_steps}, effective global batch={strategy.global_batch * cfg.accum_steps}, "
           f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}, "
-          f"label_smoothing={cfg.label_smoothing:g}", flush=True)
+          f"label_smoothing={cfg.label_smoothing:g}, global_clipnorm={cfg.global_clipnorm}, "
+          f"skip_nonfinite={cfg.skip_nonfinite}", flush=True)
 
 
 def model_summary(cfg) -> str:
@@ -42,6 +43,7 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
     cfg = config_from_args(preset, argv, extra)
     try:
         check_loss(cfg)
+        check_clip(cfg)
     except ValueError as e:
         sys.stderr.write(f"{e}\n")
         return 2

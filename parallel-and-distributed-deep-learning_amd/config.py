@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -51,6 +52,9 @@ class TrainConfig:
     label_smoothing: float = 0.0                   # eps of the loss target (1 - eps) * onehot + eps / num_classes
                                                    # (Keras CategoricalCrossentropy(label_smoothing)); training,
                                                    # validation and --evaluate all report this loss
+    global_clipnorm: Optional[float] = None        # additive (Keras `global_clipnorm`): the whole gradient is scaled
+                                                   # by C / max(|g|, C) before the update; None = off
+    skip_nonfinite: bool = False                   # additive: a step whose gradient norm is inf / nan updates nothing
     # training loop
     epochs: int = 50                               # imagenet-resnet50.py:67
     verbose: int = 2
@@ -156,6 +160,18 @@ def check_loss(cfg: TrainConfig) -> None:
         raise ValueError(f"--label-smoothing must be a number in [0, 1] (got {eps!r})")
 
 
+def check_clip(cfg: TrainConfig) -> None:
+    """--global-clipnorm C / --skip-nonfinite: a threshold that is no finite number > 0, or either
+    option on the parameter server, is a configuration error, raised before anything is built."""
+    c = cfg.global_clipnorm
+    if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0):
+        raise ValueError(f"--global-clipnorm must be a finite number > 0 (got {c!r})")
+    if cfg.strategy == "ps" and (c is not None or cfg.skip_nonfinite):
+        raise ValueError("--global-clipnorm / --skip-nonfinite are not supported for --strategy ps: every parameter-"
+                         "server shard applies its own Adam to one worker's push, so no process holds a whole "
+                         "gradient to take the global norm of")
+
+
 def make_config(preset: str = "single", **overrides) -> TrainConfig:
     if preset not in PRESETS:
         raise ValueError(f"unknown preset {preset!r}; choose from {sorted(PRESETS)}")
@@ -185,6 +201,13 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--label-smoothing", type=float, dest="label_smoothing",
       help="eps in [0, 1]: the loss target is (1 - eps) * onehot + eps / num_classes (0.1 in the large-batch "
            "recipes); loss, val_loss and --evaluate all report the smoothed loss")
+    a("--global-clipnorm", type=float, dest="global_clipnorm",
+      help="C > 0: scale the whole gradient by C / max(|g|, C) before the update (Keras global_clipnorm), the norm "
+           "taken on the device in a fixed order; with --accum-steps K the optimizer only runs on the K-th "
+           "micro-step, so the norm is that of the folded mean gradient; not with --strategy ps")
+    a("--skip-nonfinite", action="store_true", default=None, dest="skip_nonfinite",
+      help="a step whose gradient norm is inf / nan leaves parameters and optimizer state untouched (the step "
+           "count still advances); not with --strategy ps")
     a("--lr-schedule", choices=["plateau", "poly"], dest="lr_schedule",
       help="plateau: ReduceLROnPlateau (+ the Horovod warm-up); poly: per-step linear warm-up over "
            "--warmup-epochs, then power-2 decay to --lr-end at the last step, computed on the device")

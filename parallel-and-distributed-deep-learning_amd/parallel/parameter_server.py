@@ -826,8 +826,9 @@ def run_ps_job(cfg, num_ps: Optional[int] = None, num_workers: Optional[int] = N
     """Entry of imagenet-resnet50-ps.py.  Under torchrun (WORLD_SIZE = P + W) every process
     takes its role from RANK; otherwise spawn the whole cluster locally (the reference's
     create_in_process_cluster, imagenet-resnet50-ps.py:31-65)."""
-    from ..config import check_accum, check_loss
+    from ..config import check_accum, check_clip, check_loss
     check_accum(cfg)                              # (--accum-steps > 1: every push is one asynchronous update)
+    check_clip(cfg)                               # (no process here holds a whole gradient to take the norm of)
     check_loss(cfg)                               # (--label-smoothing: every worker's own loss head takes it)
     ns = getattr(cfg, "_ns", None)
     if ns is not None and (num_ps is None or num_workers is None):

@@ -123,9 +123,10 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
-        from ..config import check_accum, check_loss
+        from ..config import check_accum, check_clip, check_loss
         check_accum(cfg)
         check_loss(cfg)
+        check_clip(cfg)
         self.cfg = cfg
         self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
         self.rank = 0
@@ -181,7 +182,8 @@ class Strategy:
         opt = make_optimizer(self.cfg.optimizer, eng, lr=self.cfg.lr, momentum=self.cfg.momentum,
                              nesterov=self.cfg.nesterov, weight_decay=self.cfg.weight_decay, beta1=self.cfg.beta1,
                              beta2=self.cfg.beta2, eps=self.cfg.adam_eps, lars_eta=self.cfg.lars_eta,
-                             lars_eps=self.cfg.lars_eps)
+                             lars_eps=self.cfg.lars_eps, global_clipnorm=self.cfg.global_clipnorm,
+                             skip_nonfinite=self.cfg.skip_nonfinite)
         return eng, opt
 
     def _build(self, trainer):
@@ -632,7 +634,8 @@ class _LocalReplicas:
             eng.init(seed=cfg.seed)
             opt = make_optimizer(cfg.optimizer, eng, lr=cfg.lr, momentum=cfg.momentum, nesterov=cfg.nesterov,
                                  weight_decay=cfg.weight_decay, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.adam_eps,
-                                 lars_eta=cfg.lars_eta, lars_eps=cfg.lars_eps)
+                                 lars_eta=cfg.lars_eta, lars_eps=cfg.lars_eps, global_clipnorm=cfg.global_clipnorm,
+                                 skip_nonfinite=cfg.skip_nonfinite)
             self.replicas.append((eng, opt))
             self.augs.append(Augment(cfg, d, cfg.seed + 7919 * (global_rank_base + i)))
         self.comm = None

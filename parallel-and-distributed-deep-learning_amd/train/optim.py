@@ -25,13 +25,25 @@ def scheduled_lr(lr: float, t: int, warmup_steps: int, total_steps: int, end_lr:
     return end_lr
 
 
+GRAD_NORM_CHUNK = 16384  # floats per block of the global-norm pass (kGradNormDefaultChunk)
+
+
 class FlatOptimizer:
     """On the GPU the step counter and learning rate live in a device buffer
     `hs = {t, lr, lr_t, lr_sched, warmup_steps, total_steps, end_lr, -}` advanced by a
     one-thread kernel, so a captured step (HIP graph) replays correctly; host-side changes (LR
     callbacks, checkpoint restore) are written to it before the next step, outside any capture.
     With a schedule (`set_schedule`) that kernel also derives the step's learning rate from the
-    step count, so a per-step schedule costs no host write at all."""
+    step count, so a per-step schedule costs no host write at all.
+
+    Global-norm clipping and the non-finite skip (`set_grad_clip`, both off by default) add one
+    norm pass before the update: `gn = {norm, scale, skip, clip, skip_enabled, clipped steps,
+    skipped steps, -}` is a second device buffer, filled by `native.grad_norm` in a fixed
+    reduction order (bit-identical on every replica) and read by the update kernel, which
+    multiplies `scale = clip / max(norm, clip)` into the gradient scale and does nothing at all
+    when `skip` is set.  The threshold is host-written like `lr`, so a captured step replays with
+    a changed threshold.  With both off, `gn` is None and a step makes exactly the calls it made
+    before."""
 
     def __init__(self, engine, lr: float):
         self.engine = engine
@@ -44,6 +56,11 @@ class FlatOptimizer:
         self._iterations = 0         # Keras `optimizer.iterations`
         self._dirty = True
         self._sched = None           # (warmup_steps, total_steps, end_lr) or None
+        self._clip = None            # global_clipnorm threshold or None
+        self._skip_nonfinite = False
+        self.gn = None               # device float[8] (a host list on the CPU) while clipping / skipping is on
+        self.gn_partials = None      # one float per chunk of the norm pass
+        self.gn_chunk = GRAD_NORM_CHUNK
 
     @property
     def on_gpu(self):
@@ -92,12 +109,71 @@ class FlatOptimizer:
         """The rate of the most recent step (the base rate before the first)."""
         return self.lr_at(max(self._iterations, 1)) if self._sched is not None else self._lr
 
+    def set_grad_clip(self, global_clipnorm=None, skip_nonfinite=False):
+        """`global_clipnorm` C (Keras): the whole gradient is scaled by C / max(norm, C), norm the
+        L2 norm of gscale * grads over all trainable parameters; None measures only.
+        `skip_nonfinite`: a step whose norm is inf / nan (some non-finite gradient, or an fp32
+        overflow of the sum of squares) changes neither the parameters nor the optimizer state;
+        `iterations` still advances.  With either on, `clip_stats()` reports the norm.  Turn
+        them on before the step is captured into a graph (the capture records the norm pass); a
+        later change of the threshold reaches the next replay through `sync_hparams`."""
+        if global_clipnorm is not None:
+            c = global_clipnorm
+            if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
+                raise ValueError(f"global_clipnorm must be a finite number > 0 (got {c!r})")
+        self._clip = None if global_clipnorm is None else float(global_clipnorm)
+        self._skip_nonfinite = bool(skip_nonfinite)
+        if not self.clip_active:
+            self.gn = self.gn_partials = None
+        elif self.gn is None:
+            if self.on_gpu:
+                dev = self.params.device
+                self.gn = torch.zeros(8, dtype=torch.float32, device=dev)
+                self.gn[1] = 1.0
+                self.gn_partials = torch.zeros(-(-self.n // self.gn_chunk), dtype=torch.float32, device=dev)
+            else:
+                self.gn = [0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+        self._dirty = True
+
+    @property
+    def clip_active(self) -> bool:
+        return self._clip is not None or self._skip_nonfinite
+
+    @property
+    def global_clipnorm(self):
+        return self._clip
+
+    @property
+    def skip_nonfinite(self) -> bool:
+        return self._skip_nonfinite
+
+    def clip_stats(self):
+        """{"norm", "scale"} of the most recent step (the norm before clipping) and the counts
+        {"clipped", "skipped"} since the last `reset_clip_counters()`; one device-to-host copy.
+        None while neither clipping nor the skip is on."""
+        if self.gn is None:
+            return None
+        if self.on_gpu:
+            torch.cuda.synchronize(self.params.device)   # (the step may have run on a replica's own stream)
+        gn = self.gn.cpu().tolist() if self.on_gpu else self.gn
+        return {"norm": gn[0], "scale": gn[1], "clipped": int(gn[5]), "skipped": int(gn[6])}
+
+    def reset_clip_counters(self):
+        if self.gn is not None:
+            if self.on_gpu:
+                self.gn[5:7].zero_()
+            else:
+                self.gn[5] = self.gn[6] = 0.0
+
     def sync_hparams(self):
-        """Write host-side lr / step count / schedule into the device buffer (never inside a capture)."""
+        """Write host-side lr / step count / schedule (and the clip threshold and skip switch) into
+        the device buffers (never inside a capture)."""
         if self.hs is not None and self._dirty:
             wu, tot, end = self._sched or (0, 0, 0.0)
             self.hs.copy_(torch.tensor([float(self._iterations), self._lr, 0.0, 0.0, float(wu), float(tot), end, 0.0]),
                           non_blocking=False)
+            if self.gn is not None:
+                self.gn[3:5].copy_(torch.tensor([self._clip or 0.0, float(self._skip_nonfinite)]), non_blocking=False)
             self._dirty = False
 
     def _device_step(self, adam: bool, b1=0.0, b2=0.0):
@@ -108,6 +184,24 @@ class FlatOptimizer:
             native.opt_hparams(self.hs, b1, b2, adam)
         else:
             native.opt_hparams_sched(self.hs, b1, b2, adam)
+        if self.gn is not None:
+            native.grad_norm(self.grads[: self.n], self.gscale, self.gn_chunk, self.gn_partials, self.gn)
+
+    def _host_clip(self):
+        """CPU form of the norm pass: (skip, gradient scale including the clip scale).  The norm
+        is taken in float64; the scale formula and the counters are the device's."""
+        if self.gn is None:
+            return False, self.gscale
+        gn = self.gn
+        gn[3], gn[4] = self._clip or 0.0, float(self._skip_nonfinite)
+        g = self.grads[: self.n].double() * self.gscale
+        norm = float((g * g).sum().sqrt())
+        scale = gn[3] / norm if gn[3] > 0 and norm > gn[3] else 1.0
+        skip = bool(gn[4]) and not math.isfinite(norm)
+        gn[0], gn[1], gn[2] = norm, scale, float(skip)
+        gn[5] += scale < 1.0 and not skip
+        gn[6] += skip
+        return skip, self.gscale * scale
 
     def state_tensors(self):
         return {}
@@ -125,12 +219,16 @@ class Adam(FlatOptimizer):
             from ..ops.native import native
             self._device_step(True, self.b1, self.b2)
             self._iterations += 1
-            native.adam(self.params, self.grads, self.m, self.v, 0.0, self.b1, self.b2, self.eps, self.gscale, self.hs)
+            native.adam(self.params, self.grads, self.m, self.v, 0.0, self.b1, self.b2, self.eps, self.gscale, self.hs,
+                        self.gn)
         else:
             self._iterations += 1
+            skip, gs = self._host_clip()
+            if skip:
+                return
             t = self._iterations
             lr_t = self.lr_at(t) * math.sqrt(1 - self.b2 ** t) / (1 - self.b1 ** t)
-            g = self.grads * self.gscale
+            g = self.grads * gs
             self.m.mul_(self.b1).add_(g, alpha=1 - self.b1)
             self.v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
             self.params.sub_(lr_t * self.m / (self.v.sqrt() + self.eps))
@@ -150,11 +248,15 @@ class SGD(FlatOptimizer):
             from ..ops.native import native
             self._device_step(False)
             self._iterations += 1
-            native.sgd(self.params, self.grads, self.mom, 0.0, self.mu, self.wd, self.nesterov, self.gscale, self.hs)
+            native.sgd(self.params, self.grads, self.mom, 0.0, self.mu, self.wd, self.nesterov, self.gscale, self.hs,
+                       self.gn)
         else:
             self._iterations += 1
+            skip, gs = self._host_clip()
+            if skip:
+                return
             lr = self.lr_at(self._iterations)
-            g = self.grads * self.gscale + self.wd * self.params
+            g = self.grads * gs + self.wd * self.params
             self.mom.mul_(self.mu).sub_(lr * g)
             if self.nesterov:
                 self.params.add_(self.mu * self.mom - lr * g)
@@ -233,13 +335,16 @@ class LARS(FlatOptimizer):
             self._device_step(False)
             self._iterations += 1
             native.lars(self.params, self.grads, self.mom, self.table, self.table_host, self.chunk, self.partials,
-                        self.ratios, 0.0, self.mu, self.wd, self.eta, self.eps, self.gscale, self.hs)
+                        self.ratios, 0.0, self.mu, self.wd, self.eta, self.eps, self.gscale, self.hs, self.gn)
         else:
             self._iterations += 1
+            skip, gs = self._host_clip()
+            if skip:
+                return
             lr = self.lr_at(self._iterations)
             for i, (off, size, adapt, _) in enumerate(self.segments):
                 w = self.params[off:off + size]
-                g = self.grads[off:off + size] * self.gscale
+                g = self.grads[off:off + size] * gs
                 v = self.mom[off:off + size]
                 ratio, wd = 1.0, 0.0
                 if adapt:
@@ -261,6 +366,13 @@ class LARS(FlatOptimizer):
 
 
 def make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
+    opt = _make_optimizer(name, engine, lr, **kw)
+    if kw.get("global_clipnorm") is not None or kw.get("skip_nonfinite"):
+        opt.set_grad_clip(kw.get("global_clipnorm"), bool(kw.get("skip_nonfinite")))
+    return opt
+
+
+def _make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
     if name == "lars":
         return LARS(engine, lr, kw.get("momentum", 0.9), kw.get("weight_decay", 0.0), kw.get("lars_eta", 1e-3),
                     kw.get("lars_eps", 0.0), kw.get("nesterov", False))

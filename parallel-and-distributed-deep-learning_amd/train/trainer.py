@@ -170,6 +170,13 @@ class Trainer:
                 break
             for cb in cbs:
                 cb.on_epoch_begin(epoch)
+            # --global-clipnorm / --skip-nonfinite: replica 0's optimizer reports (every replica's
+            # norm is bit-identical); the counts are per epoch
+            clip_opt = st._replicas()[0][1] if hasattr(st, "_replicas") else None
+            if clip_opt is not None and not getattr(clip_opt, "clip_active", False):
+                clip_opt = None
+            if clip_opt is not None:
+                clip_opt.reset_clip_counters()
             self.log(f"Epoch {epoch + 1}/{epochs}")
             t0 = time.time()
             acc = torch.zeros(2, dtype=torch.float64, device=st.metrics_device)
@@ -202,6 +209,11 @@ class Trainer:
                 logs["val_loss"] = vt[0] / max(vt[3], 1)
                 logs["val_accuracy"] = vt[1] / max(vt[3], 1)
             logs = {k: float(v) for k, v in logs.items()}
+            if clip_opt is not None:
+                cs = clip_opt.clip_stats()
+                logs["grad_norm"] = float(cs["norm"])     # the last update's norm, before clipping
+                logs["clipped_steps"] = cs["clipped"]
+                logs["skipped_steps"] = cs["skipped"]
             if self.schedule is not None:         # the rate of the epoch's last step, for the line and the JSONL
                 self.lr = logs["lr"] = self._scheduled_lr((epoch + 1) * spe // K)
             dt = time.time() - t0
