@@ -50,6 +50,13 @@ int ld(const Tensor& t) {
   return t.dim() >= 2 ? (int)t.stride(-2) : (int)t.size(-1);
 }
 int old(const OptT& t) { return t.has_value() ? ld(*t) : 0; }
+// The mixup / CutMix table of a batch of B images (kernels.h), or null.
+const int32_t* mix_table(const OptT& t, int64_t B) {
+  if (!t.has_value()) return nullptr;
+  PCHECK(t->is_cuda() && t->scalar_type() == torch::kInt32 && t->is_contiguous() && t->dim() == 2 &&
+         t->size(1) == 8 && t->size(0) >= B, "mix: contiguous device int32 [>= B][8]");
+  return t->data_ptr<int32_t>();
+}
 
 // Split-K workspace (fp32 partial tiles of the small-M layers, igemm.hip), owned by the
 // calling engine and made current for the calling THREAD (`splitk_use`): two engines whose
@@ -458,12 +465,12 @@ void colsum_f32(Tensor g, int64_t C, Tensor out) {
   ok(pddl::colsum_f32_launch(f32p(g), g.numel() / ld(g), (int)C, ld(g), f32p(out), cur_stream()), "colsum_f32");
 }
 void softmax_xent_f32(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
-                      Tensor correct, double smoothing) {
+                      Tensor correct, double smoothing, OptT mix) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
   PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "softmax_xent_f32: smoothing must be in [0, 1]");
   ok(pddl::softmax_xent_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
                                (int)ncls, (float)gscale, f32p(dlogits), ld(dlogits), f32p(loss_sum),
-                               f32p(correct), cur_stream(), (float)smoothing),
+                               f32p(correct), cur_stream(), (float)smoothing, mix_table(mix, logits.size(0))),
      "softmax_xent_f32");
 }
 void prep_f32(Tensor params, Tensor table, int64_t nlayers, Tensor wf32, Tensor scale, Tensor shift, double eps) {
@@ -491,7 +498,7 @@ void wgrad_f32(Tensor x, int64_t R, int64_t S, int64_t stride, int64_t pad, Tens
 }
 
 void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_t oy, int64_t ox, Tensor out,
-              OptT crop_dev) {
+              OptT crop_dev, OptT mix) {
   pddl::StemParams p{};
   PCHECK(in.is_cuda() && in.is_contiguous() && in.dim() == 4 && in.size(3) == 3, "stem input must be [B,H,W,3]");
   PCHECK(in.scalar_type() == torch::kUInt8 || in.scalar_type() == torch::kFloat32, "stem input uint8 or fp32");
@@ -509,6 +516,7 @@ void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_
     PCHECK(flip->scalar_type() == torch::kUInt8 && flip->numel() == p.B && flip->is_cuda(), "flip flags [B] uint8");
     p.flip = flip->data_ptr<uint8_t>();
   }
+  p.mix = mix_table(mix, p.B);
   p.scale = 1.f / 255.f;
   p.Hs = (int)((Hc + 6) / 2); p.Ws = (int)((Wc + 6) / 2);
   PCHECK(out.is_contiguous() && out.numel() >= (int64_t)p.B * p.Hs * p.Ws * 16, "stem s2d output too small");
@@ -683,12 +691,12 @@ void colsum_reduce(Tensor part, Tensor table, int64_t nlayers, Tensor colsum) {
      "colsum_reduce");
 }
 void softmax_xent(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
-                  Tensor correct, double smoothing) {
+                  Tensor correct, double smoothing, OptT mix) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
   PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "softmax_xent: smoothing must be in [0, 1]");
   ok(pddl::softmax_xent_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0),
                                (int)ncls, (float)gscale, bfpm(dlogits), ld(dlogits), f32p(loss_sum),
-                               f32p(correct), cur_stream(), (float)smoothing),
+                               f32p(correct), cur_stream(), (float)smoothing, mix_table(mix, logits.size(0))),
      "softmax_xent");
 }
 void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out, double smoothing) {
@@ -953,10 +961,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gap_bwd_f32", &gap_bwd_f32, REL);
   m.def("colsum_f32", &colsum_f32, REL);
   m.def("softmax_xent_f32", &softmax_xent_f32, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"),
-        py::arg("gscale"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0);
+        py::arg("gscale"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
+        py::arg("mix") = py::none());
   m.def("prep_f32", &prep_f32, REL);
   m.def("wgrad_f32", &wgrad_f32, REL);
-  m.def("stem_s2d", &stem_s2d, REL);
+  m.def("stem_s2d", &stem_s2d, REL, py::arg("images"), py::arg("flip"), py::arg("mode"), py::arg("Hc"), py::arg("Wc"),
+        py::arg("oy"), py::arg("ox"), py::arg("out"), py::arg("crop_dev"), py::arg("mix") = py::none());
   m.def("stem_wgrad_fold", &stem_wgrad_fold, REL);
   m.def("maxpool_fwd", &maxpool_fwd, REL);
   m.def("stem_pool_bwd", &stem_pool_bwd, REL, py::arg("x2"), py::arg("gpool"), py::arg("idx"), py::arg("dw"),
@@ -978,7 +988,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gap_bwd", &gap_bwd, REL);
   m.def("colsum", &colsum, REL);
   m.def("softmax_xent", &softmax_xent, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("gscale"),
-        py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0);
+        py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
+        py::arg("mix") = py::none());
   m.def("eval_metrics", &eval_metrics, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("k"),
         py::arg("out"), py::arg("smoothing") = 0.0);
   m.def("colsum_reduce", &colsum_reduce, REL);

@@ -42,7 +42,36 @@ __device__ __forceinline__ float stem_pix(const StemParams& p, int b, int y, int
   return v * p.scale;
 }
 
+// Mixup / CutMix (MIX forms; p.mix is the per-image table [B][8] of kernels.h): image b's pixel
+// becomes w*A_b + (1 - w)*A_partner with w = 0 inside the row's box and w = w_pix outside, both
+// A's being stem_pix values (each image's own flip, the batch's crop).  The partner is clamped to
+// [0, B) and the box to the image, so a bad table gives a wrong picture, never a stray read.
+struct StemMix { int pb, y0, x0, y1, x1; float w; };
+__device__ __forceinline__ StemMix stem_mix_row(const StemParams& p, int b) {
+  const int32_t* r = p.mix + (long)b * 8;
+  StemMix m;
+  m.pb = min(max(r[0], 0), p.B - 1);
+  m.y0 = min(max(r[1], 0), p.Hc); m.x0 = min(max(r[2], 0), p.Wc);
+  m.y1 = min(max(r[3], 0), p.Hc); m.x1 = min(max(r[4], 0), p.Wc);
+  m.w = __int_as_float(r[5]);
+  return m;
+}
+__device__ __forceinline__ float stem_mix_weight(const StemMix& m, int y, int x) {
+  return (y >= m.y0 && y < m.y1 && x >= m.x0 && x < m.x1) ? 0.f : m.w;
+}
+// One explicit fma in every stem kernel (the row form stays bitwise equal to the per-pixel form);
+// w = 1 returns a and w = 0 returns b bit for bit.
+__device__ __forceinline__ float stem_mix_blend(float w, float a, float b) { return __fmaf_rn(w, a, (1.f - w) * b); }
+template <bool MIX>
+__device__ __forceinline__ float stem_val(const StemParams& p, const StemMix& m, float w, int b, int y, int x, int c) {
+  if (!MIX) return stem_pix(p, b, y, x, c);
+  const float a = w != 0.f ? stem_pix(p, b, y, x, c) : 0.f;       // a side of weight 0 is not fetched
+  const float o = w != 1.f ? stem_pix(p, m.pb, y, x, c) : 0.f;
+  return stem_mix_blend(w, a, o);
+}
+
 // Space-to-depth stem input: one thread per s2d pixel, two 16-byte stores.
+template <bool MIX>
 __global__ void stem_s2d_kernel(StemParams p, int npix, uint64_t mg_ws, uint64_t mg_hs) {
   if (p.crop_dev) { p.oy = p.crop_dev[0]; p.ox = p.crop_dev[1]; }   // graph-replayable crop offset
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += gridDim.x * blockDim.x) {
@@ -50,13 +79,16 @@ __global__ void stem_s2d_kernel(StemParams p, int npix, uint64_t mg_ws, uint64_t
     const int j = q - t * p.Ws;
     const int b = fdiv(t, mg_hs);
     const int i = t - b * p.Hs;
+    StemMix m{};
+    if (MIX) m = stem_mix_row(p, b);
     float v[16];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const int y = 2 * i + (d >> 1) - 3, x = 2 * j + (d & 1) - 3;
       const bool in = y >= 0 && y < p.Hc && x >= 0 && x < p.Wc;
+      const float w = MIX ? stem_mix_weight(m, y, x) : 1.f;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[d * 4 + c] = in ? stem_pix(p, b, y, x, c) : 0.f;
+      for (int c = 0; c < 3; ++c) v[d * 4 + c] = in ? stem_val<MIX>(p, m, w, b, y, x, c) : 0.f;
       v[d * 4 + 3] = 0.f;
     }
     uint4* o = reinterpret_cast<uint4*>(p.out + (long)q * 16);
@@ -66,6 +98,7 @@ __global__ void stem_s2d_kernel(StemParams p, int npix, uint64_t mg_ws, uint64_t
 }
 
 // fp32 form (the reference-precision engine): same values, 16 fp32 channels per s2d pixel.
+template <bool MIX>
 __global__ void stem_s2d_f32_kernel(StemParams p, float* __restrict__ out, int npix, uint64_t mg_ws, uint64_t mg_hs) {
   if (p.crop_dev) { p.oy = p.crop_dev[0]; p.ox = p.crop_dev[1]; }
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < npix; q += gridDim.x * blockDim.x) {
@@ -74,12 +107,15 @@ __global__ void stem_s2d_f32_kernel(StemParams p, float* __restrict__ out, int n
     const int b = fdiv(t, mg_hs);
     const int i = t - b * p.Hs;
     float4* o = reinterpret_cast<float4*>(out + (long)q * 16);
+    StemMix m{};
+    if (MIX) m = stem_mix_row(p, b);
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const int y = 2 * i + (d >> 1) - 3, x = 2 * j + (d & 1) - 3;
       const bool in = y >= 0 && y < p.Hc && x >= 0 && x < p.Wc;
-      o[d] = make_float4(in ? stem_pix(p, b, y, x, 0) : 0.f, in ? stem_pix(p, b, y, x, 1) : 0.f,
-                         in ? stem_pix(p, b, y, x, 2) : 0.f, 0.f);
+      const float w = MIX ? stem_mix_weight(m, y, x) : 1.f;
+      o[d] = make_float4(in ? stem_val<MIX>(p, m, w, b, y, x, 0) : 0.f, in ? stem_val<MIX>(p, m, w, b, y, x, 1) : 0.f,
+                         in ? stem_val<MIX>(p, m, w, b, y, x, 2) : 0.f, 0.f);
     }
   }
 }
@@ -88,8 +124,12 @@ const char* stem_s2d_f32_launch(const StemParams& p, float* out, hipStream_t s) 
   const long npix = (long)p.B * p.Hs * p.Ws;
   if (npix >= (1L << 31) - (1L << 24)) return "stem_s2d_f32: too many pixels for 32-bit indexing";
   const int grid = (int)lmin((npix + 255) / 256, 16384);
-  hipLaunchKernelGGL(stem_s2d_f32_kernel, dim3(grid), dim3(256), 0, s, p, out, (int)npix, fdiv_magic(p.Ws),
-                     fdiv_magic(p.Hs));
+  if (p.mix)
+    hipLaunchKernelGGL(stem_s2d_f32_kernel<true>, dim3(grid), dim3(256), 0, s, p, out, (int)npix, fdiv_magic(p.Ws),
+                       fdiv_magic(p.Hs));
+  else
+    hipLaunchKernelGGL(stem_s2d_f32_kernel<false>, dim3(grid), dim3(256), 0, s, p, out, (int)npix, fdiv_magic(p.Ws),
+                       fdiv_magic(p.Hs));
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -100,13 +140,30 @@ const char* stem_s2d_f32_launch(const StemParams& p, float* out, hipStream_t s) 
 // ran at 1.8 TB/s), then thread j assembles s2d pixel j (flip applied on the LDS read).
 // Bitwise equal to the per-pixel form (same (float)u8 * scale -> bf16).
 constexpr int STEM_ROW_MAXW = 1024;   // preprocessed width the LDS row buffer holds
+constexpr int STEM_ROW_WORDS = (STEM_ROW_MAXW * 3) / 4 + 2;
+// Stage the Wc*3 bytes at src into one LDS row buffer as aligned words; returns src's offset in the first word.
+__device__ __forceinline__ int stem_stage_row(const uint8_t* src, int Wc, uint32_t* buf) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(src) & ~uintptr_t(3);
+  const int shift = (int)(reinterpret_cast<uintptr_t>(src) - a0);
+  const int nw = (shift + Wc * 3 + 3) / 4;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(a0);
+  for (int k = threadIdx.x; k < nw; k += blockDim.x) buf[k] = w[k];
+  return shift;
+}
+// MIX: the partner's two source rows are staged next to the image's own (buffers 2, 3; each of
+// the four rows has its own alignment shift) and blended on the LDS read, each image with its own
+// flip.  A partner row that has weight 0 everywhere (w_pix = 1 and no box on that row: CutMix
+// outside the box, the identity table) is not loaded; its unread buffer then meets the factor 0,
+// and a block that stages no partner row at all runs the unmixed pixel loop (w = 1 returns the
+// image's own value bit for bit either way).
+template <bool MIX>
 __global__ void __launch_bounds__(128) stem_s2d_rows_kernel(StemParams p) {
-  __shared__ uint32_t rowbuf[2][(STEM_ROW_MAXW * 3) / 4 + 2];
+  __shared__ uint32_t rowbuf[MIX ? 4 : 2][STEM_ROW_WORDS];
   if (p.crop_dev) { p.oy = p.crop_dev[0]; p.ox = p.crop_dev[1]; }
   const int i = blockIdx.x % p.Hs, b = blockIdx.x / p.Hs;
   const int oy = p.mode == 2 ? p.oy : 0, ox = p.mode == 2 ? p.ox : 0;
   const uint8_t* in = reinterpret_cast<const uint8_t*>(p.in);
-  int shift[2];
+  int shift[MIX ? 4 : 2];
   bool rok[2];
 #pragma unroll
   for (int dy = 0; dy < 2; ++dy) {
@@ -114,28 +171,48 @@ __global__ void __launch_bounds__(128) stem_s2d_rows_kernel(StemParams p) {
     rok[dy] = y >= 0 && y < p.Hc;
     shift[dy] = 0;
     if (!rok[dy]) continue;
-    const uint8_t* src = in + (((long)b * p.Hin + y + oy) * p.Win + ox) * 3;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(src) & ~uintptr_t(3);
-    shift[dy] = (int)(reinterpret_cast<uintptr_t>(src) - a0);
-    const int nw = (shift[dy] + p.Wc * 3 + 3) / 4;
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(a0);
-    for (int k = threadIdx.x; k < nw; k += blockDim.x) rowbuf[dy][k] = w[k];
+    shift[dy] = stem_stage_row(in + (((long)b * p.Hin + y + oy) * p.Win + ox) * 3, p.Wc, rowbuf[dy]);
+  }
+  // (the table row is read after the image's own rows are under way: the block's first loads do
+  // not wait for it)
+  StemMix m{};
+  bool blend = false;   // (MIX, uniform over the block: some partner row is staged; else the unmixed loop below)
+  if (MIX) {
+    m = stem_mix_row(p, b);
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const int y = 2 * i + dy - 3;
+      shift[2 + dy] = 0;
+      const bool boxed = y >= m.y0 && y < m.y1 && m.x0 < m.x1;
+      if (rok[dy] && (m.w != 1.f || boxed)) {
+        shift[2 + dy] = stem_stage_row(in + (((long)m.pb * p.Hin + y + oy) * p.Win + ox) * 3, p.Wc, rowbuf[2 + dy]);
+        blend = true;
+      }
+    }
   }
   __syncthreads();
   const bool fl = p.flip && p.flip[b];
+  const bool flp = MIX && p.flip && p.flip[m.pb];
   const uint8_t* rb = reinterpret_cast<const uint8_t*>(&rowbuf[0][0]);
-  constexpr int ROWB = ((STEM_ROW_MAXW * 3) / 4 + 2) * 4;
+  constexpr int ROWB = STEM_ROW_WORDS * 4;
   for (int j = threadIdx.x; j < p.Ws; j += blockDim.x) {
     float v[16];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const int dy = d >> 1;
-      int x = 2 * j + (d & 1) - 3;
+      const int x = 2 * j + (d & 1) - 3;
       const bool in_ = rok[dy] && x >= 0 && x < p.Wc;
-      if (fl) x = p.Wc - 1 - x;
-      const int o = dy * ROWB + shift[dy] + x * 3;
+      const int o = dy * ROWB + shift[dy] + (fl ? p.Wc - 1 - x : x) * 3;
+      if (MIX && blend) {
+        const float w = stem_mix_weight(m, 2 * i + dy - 3, x);
+        const int op = (2 + dy) * ROWB + shift[2 + dy] + (flp ? p.Wc - 1 - x : x) * 3;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[d * 4 + c] = in_ ? (float)rb[o + c] * p.scale : 0.f;
+        for (int c = 0; c < 3; ++c)
+          v[d * 4 + c] = in_ ? stem_mix_blend(w, (float)rb[o + c] * p.scale, (float)rb[op + c] * p.scale) : 0.f;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[d * 4 + c] = in_ ? (float)rb[o + c] * p.scale : 0.f;
+      }
       v[d * 4 + 3] = 0.f;
     }
     uint4* o = reinterpret_cast<uint4*>(p.out + (((long)b * p.Hs + i) * p.Ws + j) * 16);
@@ -150,12 +227,16 @@ const char* stem_s2d_launch(const StemParams& p, hipStream_t s) {
   const long npix = (long)p.B * p.Hs * p.Ws;
   if (npix >= (1L << 31) - (1L << 24)) return "stem_s2d: too many pixels for 32-bit indexing";
   if (g_stem_variant == 1 && p.in_u8 && p.mode != 1 && p.Wc <= STEM_ROW_MAXW) {
-    hipLaunchKernelGGL(stem_s2d_rows_kernel, dim3(p.B * p.Hs), dim3(128), 0, s, p);
+    if (p.mix) hipLaunchKernelGGL(stem_s2d_rows_kernel<true>, dim3(p.B * p.Hs), dim3(128), 0, s, p);
+    else hipLaunchKernelGGL(stem_s2d_rows_kernel<false>, dim3(p.B * p.Hs), dim3(128), 0, s, p);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }
   const int grid = (int)lmin((npix + 255) / 256, 16384);
-  hipLaunchKernelGGL(stem_s2d_kernel, dim3(grid), dim3(256), 0, s, p, (int)npix, fdiv_magic(p.Ws), fdiv_magic(p.Hs));
+  if (p.mix)
+    hipLaunchKernelGGL(stem_s2d_kernel<true>, dim3(grid), dim3(256), 0, s, p, (int)npix, fdiv_magic(p.Ws), fdiv_magic(p.Hs));
+  else
+    hipLaunchKernelGGL(stem_s2d_kernel<false>, dim3(grid), dim3(256), 0, s, p, (int)npix, fdiv_magic(p.Ws), fdiv_magic(p.Hs));
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -761,11 +842,17 @@ __device__ __forceinline__ float head_row_loss(float mx, float se, float below, 
   return mx + __logf(se) - vl;
 }
 
-template <typename T, bool SMOOTH>
+// MIX (mixup / CutMix; mix is the per-image table [B][8] of kernels.h): the target is
+// w*T(y_b) + (1 - w)*T(y_p) with w = w_lab, p = the row's partner (clamped to [0, B)) and T the
+// (smoothed) one-hot above; the head gathers labels[p] itself.
+// loss += log(se) + keep*(w*(mx - z[y_b]) + (1 - w)*(mx - z[y_p])) + spread*below and
+// correct += (first argmax == (w >= 0.5 ? y_b : y_p)).  w = 1 gives the unmixed dlogits bit for bit.
+template <typename T, bool SMOOTH, bool MIX>
 __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ labels,
                                     int B, int ncls, float gscale, float keep, float spread,
                                     T* __restrict__ dl, int ldd,
-                                    float* __restrict__ loss_sum, float* __restrict__ correct) {
+                                    float* __restrict__ loss_sum, float* __restrict__ correct,
+                                    const int32_t* __restrict__ mix) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (b >= B) return;
@@ -785,10 +872,25 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, c
   float se, below;
   head_row_sums<SMOOTH>(row, ncls, lane, mx, se, below);
   const int lab = (int)labels[b];
+  int labp = lab;
+  float wl = 1.f, wp = 0.f;
+  if (MIX) {
+    labp = (int)labels[min(max(mix[(long)b * 8], 0), B - 1)];
+    wl = __int_as_float(mix[(long)b * 8 + 6]);
+    wp = 1.f - wl;
+  }
   const float inv = 1.f / se;
+  // MIX: the row's four target values, made once, so that the loop is the unmixed loop's select
+  // between row constants (w = 1: keep*1 + spread is the unmixed keep + spread, rounded once)
+  const float t_none = SMOOTH ? spread : 0.f;
+  const float t_own = SMOOTH ? keep * wl + spread : wl, t_par = SMOOTH ? keep * wp + spread : wp;
+  const float t_both = SMOOTH ? keep * (wl + wp) + spread : wl + wp;     // (the partner has the same label)
   for (int j = lane; j < ldd; j += 64) {
     float d = 0.f;
-    if (SMOOTH) {
+    if (MIX) {
+      const float t = j == lab ? (j == labp ? t_both : t_own) : (j == labp ? t_par : t_none);
+      if (j < ncls) d = (__expf(row[j] - mx) * inv - t) * gscale;
+    } else if (SMOOTH) {
       if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? keep + spread : spread)) * gscale;
     } else {
       if (j < ncls) d = (__expf(row[j] - mx) * inv - (j == lab ? 1.f : 0.f)) * gscale;
@@ -796,39 +898,51 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, int ldl, c
     dl[(long)b * ldd + j] = wcvt<T>(d);
   }
   if (lane == 0) {
-    unsafeAtomicAdd(loss_sum, head_row_loss<SMOOTH>(mx, se, below, row[lab], keep, spread));
-    unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
+    if (MIX) {
+      const float gap = wl * (mx - row[lab]) + wp * (mx - row[labp]);
+      unsafeAtomicAdd(loss_sum, SMOOTH ? __logf(se) + keep * gap + spread * below : __logf(se) + gap);
+      unsafeAtomicAdd(correct, amax == (wl >= 0.5f ? lab : labp) ? 1.f : 0.f);
+    } else {
+      unsafeAtomicAdd(loss_sum, head_row_loss<SMOOTH>(mx, se, below, row[lab], keep, spread));
+      unsafeAtomicAdd(correct, amax == lab ? 1.f : 0.f);
+    }
   }
 }
 namespace {
 bool smoothing_ok(float eps) { return eps >= 0.f && eps <= 1.f; }   // (false for a NaN)
 
+template <typename T, bool SMOOTH, bool MIX>
+void softmax_xent_go(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale, float keep,
+                     float spread, T* dlogits, int ldd, float* loss_sum, float* correct, const int32_t* mix,
+                     hipStream_t s) {
+  hipLaunchKernelGGL((softmax_xent_kernel<T, SMOOTH, MIX>), dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B,
+                     ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct, mix);
+}
 template <typename T>
 const char* softmax_xent_launch_t(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
                                   T* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
-                                  float smoothing) {
+                                  float smoothing, const int32_t* mix) {
   if (ldd < ncls) return "softmax_xent: ldd < ncls";
   if (!smoothing_ok(smoothing)) return "softmax_xent: smoothing outside [0, 1]";
   const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
-  if (smoothing > 0.f)
-    hipLaunchKernelGGL((softmax_xent_kernel<T, true>), dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B,
-                       ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct);
-  else
-    hipLaunchKernelGGL((softmax_xent_kernel<T, false>), dim3((B + 3) / 4), dim3(256), 0, s, logits, ldl, labels, B,
-                       ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct);
+  auto go = smoothing > 0.f ? (mix ? softmax_xent_go<T, true, true> : softmax_xent_go<T, true, false>)
+                            : (mix ? softmax_xent_go<T, false, true> : softmax_xent_go<T, false, false>);
+  go(logits, ldl, labels, B, ncls, gscale, keep, spread, dlogits, ldd, loss_sum, correct, mix, s);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 }  // namespace
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
                                 uint16_t* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
-                                float smoothing) {
-  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing);
+                                float smoothing, const int32_t* mix) {
+  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing,
+                               mix);
 }
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, float gscale,
                                 float* dlogits, int ldd, float* loss_sum, float* correct, hipStream_t s,
-                                float smoothing) {
-  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing);
+                                float smoothing, const int32_t* mix) {
+  return softmax_xent_launch_t(logits, ldl, labels, B, ncls, gscale, dlogits, ldd, loss_sum, correct, s, smoothing,
+                               mix);
 }
 
 // ---------------------------------------------------------------------- eval-metrics

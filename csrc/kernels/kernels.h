@@ -179,7 +179,16 @@ struct StemParams {
   const uint8_t* flip;                // per-image horizontal flip flags (nullable)
   float scale;                        // Rescaling(1/255)
   uint16_t* out; int Hs, Ws;          // space-to-depth image [B][Hs][Ws][16], Hs = (Hc + 6) / 2
+  const int32_t* mix;                 // optional mixup / CutMix table [B][8] (below); null: no mixing
 };
+// The per-image mix table, int32 [B][8], shared by the stem kernels and the training heads.  Row b:
+//   0      partner: index in this batch of the image mixed into image b
+//   1..4   y0, x0, y1, x1: half-open box in the Hc x Wc preprocessed image (after each image's own
+//          crop and flip, before the zero padding); empty when y1 <= y0 or x1 <= x0
+//   5      w_pix (float bits): weight of image b's own pixel outside the box (inside it is 0)
+//   6      w_lab (float bits): weight of image b's own label
+//   7      0 (reserved)
+// The identity row {b, 0, 0, 0, 0, 1.f, 1.f, 0} gives the unmixed result bit for bit.
 // Preprocess + ZeroPadding2D(3) + 2x2 space-to-depth: channel (dy*2+dx)*4 + c of pixel (i, j)
 // is the padded preprocessed pixel (2i+dy-3, 2j+dx-3, c) (c = 3 is zero).  The 7x7/s2 stem
 // conv then becomes a 4x4/s1 "window" implicit GEMM with K = 4*4*16 = 256.
@@ -272,13 +281,14 @@ const char* colsum_reduce_launch(const float* part, const ColRedLayer* layers_de
                                  hipStream_t s);
 int maxpool_bwd_partial_rows(int B, int H, int W, int C);
 // The training head, one kernel for both precisions: bf16 dlogits (the bf16 engines; columns
-// ncls..ldd zeroed) or fp32 dlogits (the fp32 engines).
+// ncls..ldd zeroed) or fp32 dlogits (the fp32 engines).  mix (nullable): the table above, for a
+// soft target between each row's label and its partner's.
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
                                 float gscale, uint16_t* dlogits, int ldd, float* loss_sum, float* correct,
-                                hipStream_t s, float smoothing = 0.f);
+                                hipStream_t s, float smoothing = 0.f, const int32_t* mix = nullptr);
 const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
                                 float gscale, float* dlogits, int ldd, float* loss_sum, float* correct,
-                                hipStream_t s, float smoothing = 0.f);
+                                hipStream_t s, float smoothing = 0.f, const int32_t* mix = nullptr);
 // Evaluation head (no dlogits): out[0] += loss sum, out[1] += top-1 hits, out[2] += top-k hits.
 // (smoothing: the label-smoothing eps in [0, 1] of all three loss heads; the target is
 // (1 - eps)*onehot + eps/ncls, and 0 is the plain one-hot cross-entropy)

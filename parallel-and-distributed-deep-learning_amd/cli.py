@@ -11,7 +11,7 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import check_accum, check_clip, check_loss, config_from_args
+from .config import check_accum, check_clip, check_loss, check_mix, config_from_args
 
 
 def _banner(cfg, strategy):
@@ -22,15 +22,18 @@ def _banner(cfg, strategy):
           f"accum_steps={cfg.accum_steps}, effective global batch={strategy.global_batch * cfg.accum_steps}, "
           f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}, "
           f"label_smoothing={cfg.label_smoothing:g}, global_clipnorm={cfg.global_clipnorm}, "
-          f"skip_nonfinite={cfg.skip_nonfinite}", flush=True)
+          f"skip_nonfinite={cfg.skip_nonfinite}, "
+          f"mixup={cfg.mixup:g}, cutmix={cfg.cutmix:g}, mix_prob={cfg.mix_prob:g}", flush=True)
 
 
 def model_summary(cfg) -> str:
     from .models.resnet50 import ParamLayout
     L = ParamLayout(cfg.num_classes)
+    kinds = [n for n, a in (("MixUp", cfg.mixup), ("CutMix", cfg.cutmix)) if a > 0]
+    mix = f"  batch_mix ({' / '.join(kinds)}, p={cfg.mix_prob:g})" if kinds else ""
     return (f'Model: "{cfg.model_name}"\n'
             f"  input_1 (InputLayer) [(None, {cfg.image_size}, {cfg.image_size}, 3)]\n"
-            f"  rescaling (Rescaling)  random_crop (RandomCrop {cfg.crop}x{cfg.crop})  random_flip (RandomFlip)\n"
+            f"  rescaling (Rescaling)  random_crop (RandomCrop {cfg.crop}x{cfg.crop})  random_flip (RandomFlip){mix}\n"
             f"  resnet50 (Functional) (None, 2048)   {L.count() - 2048 * cfg.num_classes - cfg.num_classes:,}\n"
             f"  dense (Dense) (None, {cfg.num_classes})  {2048 * cfg.num_classes + cfg.num_classes:,}\n"
             f"Total params: {L.count():,}\nTrainable params: {L.count(True):,}\n"
@@ -43,6 +46,7 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
     cfg = config_from_args(preset, argv, extra)
     try:
         check_loss(cfg)
+        check_mix(cfg)
         check_clip(cfg)
     except ValueError as e:
         sys.stderr.write(f"{e}\n")

@@ -52,6 +52,9 @@ class TrainConfig:
     label_smoothing: float = 0.0                   # eps of the loss target (1 - eps) * onehot + eps / num_classes
                                                    # (Keras CategoricalCrossentropy(label_smoothing)); training,
                                                    # validation and --evaluate all report this loss
+    mixup: float = 0.0                             # additive: mixup alpha (lambda ~ Beta(alpha, alpha)); 0 = off
+    cutmix: float = 0.0                            # additive: CutMix alpha; 0 = off (both on: one of the two per batch)
+    mix_prob: float = 1.0                          # probability that a training batch is mixed at all
     global_clipnorm: Optional[float] = None        # additive (Keras `global_clipnorm`): the whole gradient is scaled
                                                    # by C / max(|g|, C) before the update; None = off
     skip_nonfinite: bool = False                   # additive: a step whose gradient norm is inf / nan updates nothing
@@ -160,6 +163,17 @@ def check_loss(cfg: TrainConfig) -> None:
         raise ValueError(f"--label-smoothing must be a number in [0, 1] (got {eps!r})")
 
 
+def check_mix(cfg: TrainConfig) -> None:
+    """--mixup / --cutmix ALPHA and --mix-prob P: a negative or non-finite alpha, or P outside
+    [0, 1], is a configuration error, raised before anything is built."""
+    for flag, a in (("--mixup", cfg.mixup), ("--cutmix", cfg.cutmix)):
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or a < 0:
+            raise ValueError(f"{flag} must be a finite number >= 0 (got {a!r})")
+    p = cfg.mix_prob
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+        raise ValueError(f"--mix-prob must be a number in [0, 1] (got {p!r})")
+
+
 def check_clip(cfg: TrainConfig) -> None:
     """--global-clipnorm C / --skip-nonfinite: a threshold that is no finite number > 0, or either
     option on the parameter server, is a configuration error, raised before anything is built."""
@@ -201,6 +215,15 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--label-smoothing", type=float, dest="label_smoothing",
       help="eps in [0, 1]: the loss target is (1 - eps) * onehot + eps / num_classes (0.1 in the large-batch "
            "recipes); loss, val_loss and --evaluate all report the smoothed loss")
+    a("--mixup", type=float, metavar="ALPHA",
+      help="mixup: each training batch is blended with a permutation of itself, lambda ~ Beta(ALPHA, ALPHA), inside "
+           "the preprocess kernel, and the loss takes the matching soft target (0 = off; 0.2 in the usual recipes)")
+    a("--cutmix", type=float, metavar="ALPHA",
+      help="CutMix: a random box of each image is replaced by its partner's, lambda ~ Beta(ALPHA, ALPHA), the label "
+           "weight being the kept area (0 = off; 1.0 in the usual recipes); with --mixup, each mixed batch takes one "
+           "of the two with probability 1/2")
+    a("--mix-prob", type=float, dest="mix_prob", metavar="P",
+      help="probability in [0, 1] that a training batch is mixed (default 1; needs --mixup or --cutmix)")
     a("--global-clipnorm", type=float, dest="global_clipnorm",
       help="C > 0: scale the whole gradient by C / max(|g|, C) before the update (Keras global_clipnorm), the norm "
            "taken on the device in a fixed order; with --accum-steps K the optimizer only runs on the K-th "

@@ -49,6 +49,12 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
+def _mix_kw(mix):
+    """The `mix=` keyword of the stem and head launches: absent without a mixup / CutMix table, so
+    an unmixed step launches exactly what it always launched."""
+    return {} if mix is None else {"mix": mix}
+
+
 class HipEngine(SideStream):
     BN_MODES = ("frozen",)   # HipEngineBNTrain (models/engine_bn.py) runs bn_mode="train"
     FUSE_PROJ_OK = True     # projection blocks: conv3 + shortcut conv as one dual-source GEMM
@@ -572,7 +578,7 @@ class HipEngine(SideStream):
             return 1, 0, 0
         return 2, crop_offset[0], crop_offset[1]
 
-    def _forward(self, images, B, training, flip, crop_offset):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         mode, oy, ox = self._stem_mode(training, crop_offset)
@@ -580,7 +586,8 @@ class HipEngine(SideStream):
         crop_dev = None
         if mode == 2 and isinstance(crop_offset, torch.Tensor):   # device offsets (graph capture)
             crop_dev, oy, ox = crop_offset, 0, 0
-        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev)
+        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
+                   **_mix_kw(mix if training else None))
         H1, H2, Hs = self.H1, self.H2, self.Hs
         s = L.stem
         pool = self.pool[:B]
@@ -689,7 +696,7 @@ class HipEngine(SideStream):
 
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -699,13 +706,13 @@ class HipEngine(SideStream):
         self.ws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix)
         prof.pop()
         prof.push("step/backward")
         logits = self.logits[:B]
         dl = self.dlogits[:B]
         N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                       self.label_smoothing)
+                       self.label_smoothing, **_mix_kw(mix))
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             if not torch.cuda.is_current_stream_capturing():   # (a capture starts synchronized)
                 torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)

@@ -26,7 +26,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
-from .engine import IGEMM_DGRAD, STEM_K, HipEngine
+from .engine import IGEMM_DGRAD, STEM_K, HipEngine, _mix_kw
 from ..utils import profiling as prof
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout
 
@@ -189,7 +189,7 @@ class HipEngineBNTrain(HipEngine):
             N.bn_stats(self.acc, st, nst, maxc, True, self.params, self.bn_mean, self.bn_inv, self.bn_scale,
                        self.bn_shift, BN_EPS, BN_MOMENTUM)
 
-    def _forward(self, images, B, training, flip, crop_offset):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         tabs = self._launch_tables(B) if training else None
@@ -201,7 +201,8 @@ class HipEngineBNTrain(HipEngine):
         crop_dev = None
         if mode == 2 and isinstance(crop_offset, torch.Tensor):
             crop_dev, oy, ox = crop_offset, 0, 0
-        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev)
+        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
+                   **_mix_kw(mix if training else None))
         H1, Hs = self.H1, self.Hs
         s = L.stem
         zs = self.zs[:B]
@@ -291,7 +292,7 @@ class HipEngineBNTrain(HipEngine):
                             sg=self.bsg, sgx=self.bsgx, dz=out, grads=self.grads, coef=self.bcoef)
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -299,13 +300,13 @@ class HipEngineBNTrain(HipEngine):
         self.bws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix)
         prof.pop()
         prof.push("step/backward")
         logits = self.logits[:B]
         dl = self.dlogits[:B]
         N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                       self.label_smoothing)
+                       self.label_smoothing, **_mix_kw(mix))
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)
             self._dgrad_ready = None

@@ -29,7 +29,7 @@ import torch
 from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
-from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K
+from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 from .side_stream import SideStream
 
@@ -266,12 +266,13 @@ class HipF32Engine(SideStream):
         self._conv(x, c.k, c.stride, c.pad, out.shape[1], self._w(c.name, c.cout, c.k * c.k * c.cin), out,
                    self.scale[ch:], self.shift[ch:], res, relu)
 
-    def _forward(self, images, B, training, flip, crop_offset):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
-        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None)
+        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
+                   **_mix_kw(mix if training else None))
         s = L.stem
         c1 = self.c1[:B]
         ch = self.ch[s.name]
@@ -306,20 +307,20 @@ class HipF32Engine(SideStream):
 
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
         self.ws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix)
         prof.pop()
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
         N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                           self.label_smoothing)
+                           self.label_smoothing, **_mix_kw(mix))
         bks = buckets if buckets is not None else []
         nb = [0]
 
@@ -563,7 +564,7 @@ class HipF32EngineBNTrain(HipF32Engine):
             self.N.bn_stats(self.acc, self._stats(c, M), 1, c.cout, True, self.params, self.bn_mean, self.bn_inv,
                             self.bn_scale, self.bn_shift, BN_EPS, BN_MOMENTUM)
 
-    def _forward(self, images, B, training, flip, crop_offset):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         if not training:   # the moving statistics for every layer at once
@@ -571,7 +572,8 @@ class HipF32EngineBNTrain(HipF32Engine):
                        self.bn_scale, self.bn_shift, BN_EPS, BN_MOMENTUM)
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
-        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None)
+        N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
+                   **_mix_kw(mix if training else None))
         s = L.stem
         zs, c1 = self.zs[:B], self.c1[:B]
         self._z(s, x2, 4, 1, 0, self.H1, self.wf32[:64 * STEM_K].view(64, STEM_K), zs, training)
@@ -630,7 +632,7 @@ class HipF32EngineBNTrain(HipF32Engine):
                            self.bn_inv, self.bsg, self.bsgx, out, out2, self.grads, self.bcoef)
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -638,13 +640,13 @@ class HipF32EngineBNTrain(HipF32Engine):
         self.bws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix)
         prof.pop()
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
         N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                           self.label_smoothing)
+                           self.label_smoothing, **_mix_kw(mix))
         bks = buckets if buckets is not None else []
         nb = [0]
 

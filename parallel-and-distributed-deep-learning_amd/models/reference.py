@@ -17,9 +17,46 @@ import torch.nn.functional as F
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 
 
+def mix_rows(mix: torch.Tensor, B: int, H: int, W: int):
+    """The first B rows of a mixup / CutMix table (int32 [>= B][8]: partner, y0, x0, y1, x1, w_pix
+    bits, w_lab bits, 0) as (partner [B] int64, box [B][4] int64 clamped to the H x W image,
+    w_pix [B] fp32, w_lab [B] fp32); the partner is clamped to [0, B) as the kernels clamp it."""
+    t = mix[:B].to(torch.int32)
+    partner = t[:, 0].long().clamp(0, B - 1)
+    box = t[:, 1:5].long()
+    box = torch.stack([box[:, 0].clamp(0, H), box[:, 1].clamp(0, W), box[:, 2].clamp(0, H), box[:, 3].clamp(0, W)], 1)
+    w = t[:, 5:7].contiguous().view(torch.float32)
+    return partner, box, w[:, 0], w[:, 1]
+
+
+def mix_pixels(x: torch.Tensor, mix: torch.Tensor) -> torch.Tensor:
+    """out_b = w*x_b + (1 - w)*x_partner on preprocessed NCHW images, w = 0 inside row b's box and
+    w_pix outside (the MIX form of the stem kernels, in fp32 torch)."""
+    B, _, H, W = x.shape
+    partner, box, w_pix, _ = mix_rows(mix.to(x.device), B, H, W)
+    ys = torch.arange(H, device=x.device).view(1, H, 1)
+    xs = torch.arange(W, device=x.device).view(1, 1, W)
+    inside = ((ys >= box[:, 0].view(B, 1, 1)) & (ys < box[:, 2].view(B, 1, 1)) &
+              (xs >= box[:, 1].view(B, 1, 1)) & (xs < box[:, 3].view(B, 1, 1)))
+    w = torch.where(inside, torch.zeros((), device=x.device), w_pix.view(B, 1, 1)).unsqueeze(1)
+    return w * x + (1.0 - w) * x[partner]
+
+
+def mix_targets(labels: torch.Tensor, mix: torch.Tensor, num_classes: int, label_smoothing: float = 0.0):
+    """(soft targets [B][ncls], the label `correct` counts against [B]): t = w*T(y_b) + (1 - w)*T(y_p)
+    with w = w_lab and T(y) = (1 - eps)*onehot(y) + eps/ncls; the counted label is the one of the
+    larger weight, image b's own on a tie (Keras's categorical accuracy on a soft target)."""
+    B = labels.shape[0]
+    partner, _, _, w_lab = mix_rows(mix.to(labels.device), B, 0, 0)
+    T = F.one_hot(labels, num_classes).float() * (1.0 - label_smoothing) + label_smoothing / num_classes
+    w = w_lab.view(B, 1)
+    return w * T + (1.0 - w) * T[partner], torch.where(w_lab >= 0.5, labels, labels[partner])
+
+
 def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[torch.Tensor] = None,
-               crop_offset=(0, 0)) -> torch.Tensor:
-    """[B,H,W,3] uint8/float (0..255) -> NCHW float32 in [0,1] at crop x crop."""
+               crop_offset=(0, 0), mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B,H,W,3] uint8/float (0..255) -> NCHW float32 in [0,1] at crop x crop.  mix (training
+    only): a mixup / CutMix table, applied after each image's own crop and flip."""
     x = images.float().permute(0, 3, 1, 2) * (1.0 / 255.0)
     H, W = x.shape[-2:]
     if crop > H or crop > W or (not training and crop != H):
@@ -30,6 +67,8 @@ def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[t
     if training and flip is not None:
         f = flip.to(torch.bool).to(x.device)
         x = torch.where(f.view(-1, 1, 1, 1), x.flip(-1), x)
+    if training and mix is not None:
+        x = mix_pixels(x, mix)
     return x
 
 
@@ -217,21 +256,29 @@ class TorchEngine:
     def after_update(self):
         pass
 
-    def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0), bucket_cb=None, buckets=None):
+    def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0), bucket_cb=None, buckets=None,
+                         mix=None):
         # leaf over the trainable prefix; BN statistics are read (and, in train mode,
         # updated in place) straight from the flat buffer
         # (a copy: BN statistics share the flat buffer and train-mode BN updates them in place)
         p = self.params[: self.L.n_trainable].clone().requires_grad_(True)
         self.model.stats = self.params
         self.model.bind(p)
-        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset)
+        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix)
         logits = self.model.logits(p, x, training=True)
-        lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
+        lab = counted = labels.to(self.device)
+        if mix is not None:
+            target, counted = mix_targets(lab, mix, logits.shape[1], self.label_smoothing)
+            if bool((mix_rows(mix, lab.shape[0], 0, 0)[3] == 1.0).all()):
+                mix = None     # every label keeps weight 1 (the identity table): the integer-label loss, bit for bit
+        if mix is None:
+            loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
+        else:      # the soft target between each label and its partner's (smoothing is inside it)
+            loss_sum = F.cross_entropy(logits, target, reduction="sum")
         (loss_sum * gscale).backward()
         with torch.no_grad():
             self.grads.copy_(p.grad)
-            correct = (logits.argmax(1) == lab).sum().float()
+            correct = (logits.argmax(1) == counted).sum().float()
             stats = torch.stack([loss_sum.detach(), correct])
         if bucket_cb is not None:   # autograd produces every gradient at once: all buckets ready
             for i in range(len(buckets) if buckets is not None else 1):

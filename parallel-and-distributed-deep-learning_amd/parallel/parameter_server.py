@@ -826,7 +826,8 @@ def run_ps_job(cfg, num_ps: Optional[int] = None, num_workers: Optional[int] = N
     """Entry of imagenet-resnet50-ps.py.  Under torchrun (WORLD_SIZE = P + W) every process
     takes its role from RANK; otherwise spawn the whole cluster locally (the reference's
     create_in_process_cluster, imagenet-resnet50-ps.py:31-65)."""
-    from ..config import check_accum, check_clip, check_loss
+    from ..config import check_accum, check_clip, check_loss, check_mix
+    check_mix(cfg)                                # (--mixup / --cutmix: every worker mixes its own batches)
     check_accum(cfg)                              # (--accum-steps > 1: every push is one asynchronous update)
     check_clip(cfg)                               # (no process here holds a whole gradient to take the norm of)
     check_loss(cfg)                               # (--label-smoothing: every worker's own loss head takes it)
@@ -922,7 +923,7 @@ class ParameterServerStrategy:
         if cl.device.type == "cuda" and hasattr(eng, "wbf") and cfg.graphs is True:
             from ..train.graph import GraphedTrainStep   # forward + backward as one HIP graph
             self.graphed = GraphedTrainStep(eng, None, cfg.batch_size, (cfg.image_size, cfg.image_size),
-                                            1.0 / cfg.batch_size, with_optimizer=False)
+                                            1.0 / cfg.batch_size, with_optimizer=False, mix=self.aug.mixing)
         self.acc = torch.zeros(2, dtype=torch.float64, device=cl.device)
         self.n_img = 0
 
@@ -935,9 +936,9 @@ class ParameterServerStrategy:
         flip, off = self.aug(B)
         g = self.graphed
         if g is not None and B == g.B and tuple(images.shape[1:3]) == tuple(g.images.shape[1:3]):
-            s = g(images, labels, flip, off)
+            s = g(images, labels, flip, off, self.aug.mix(B, graphed=True))
         else:
-            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off)
+            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=self.aug.mix(B))
         self.acc.add_(s[:2])            # (device-side: no per-step device -> host read)
         self.n_img += B
         if self.cfg.ps_overlap:

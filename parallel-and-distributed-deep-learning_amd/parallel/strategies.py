@@ -26,6 +26,7 @@ import torch.distributed as dist
 
 from ..data.datasets import Pipeline, make_source
 from ..models.resnet50 import ParamLayout
+from ..train.mix import COLS, MixSampler, identity_table
 from ..train.optim import make_optimizer
 from ..utils import profiling as prof
 from ..utils.envopts import opt
@@ -100,13 +101,57 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
 
 
 class Augment:
-    """RandomFlip (per image) and RandomCrop offset (per batch, crop < input) draws."""
+    """RandomFlip (per image) and RandomCrop offset (per batch, crop < input) draws, and the
+    mixup / CutMix table of --mixup / --cutmix (`mix`; train/mix.py)."""
+
+    MIX_STAGES = 4     # pinned staging buffers of the table upload, used in turn
 
     def __init__(self, cfg, device, seed):
         self.cfg = cfg
         self.device = device
         self.gen = torch.Generator(device=device).manual_seed(seed)
         self.rng = np.random.default_rng(seed)
+        # (a generator of its own: the flip / crop draws above are the same with mixing on or off)
+        self.sampler = MixSampler(getattr(cfg, "mixup", 0.0), getattr(cfg, "cutmix", 0.0),
+                                  getattr(cfg, "mix_prob", 1.0), cfg.crop, cfg.crop, seed)
+        self._stage = []       # [(pinned host table, event of its last upload)]
+        self._turn = 0
+
+    @property
+    def mixing(self) -> bool:
+        return self.sampler.enabled
+
+    def mix(self, B, graphed=False):
+        """The device table [B][8] of this batch's mixup / CutMix draws; None when mixing is off
+        or (with probability 1 - mix_prob) this batch is not mixed -- for a graphed step, whose
+        captured kernels always read a table, the identity table instead.  Drawn on the host and
+        uploaded with one non-blocking copy from a pinned buffer; a buffer is rewritten only
+        MIX_STAGES uploads later and only if its own upload's event has completed (no wait: a
+        buffer still in flight is replaced by a new one)."""
+        if not self.mixing:
+            return None
+        t = self.sampler.draw(B)
+        if t is None:
+            if not graphed:
+                return None
+            t = identity_table(B)
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            return torch.from_numpy(t)
+        if not self._stage:
+            self._stage = [[None, None] for _ in range(self.MIX_STAGES)]
+        slot = self._stage[self._turn % self.MIX_STAGES]
+        self._turn += 1
+        if slot[0] is None or slot[0].shape[0] < B or not slot[1].query():
+            # (first use, a larger batch, or -- the host more than MIX_STAGES steps ahead -- an upload
+            # still in flight: a fresh buffer, never a wait; the copy keeps the old one alive)
+            slot[0] = torch.empty(B, COLS, dtype=torch.int32).pin_memory()
+        host = slot[0][:B]
+        host.copy_(torch.from_numpy(t))
+        out = host.to(dev, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(dev))
+        return out
 
     def __call__(self, B):
         flip = None
@@ -123,9 +168,10 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
-        from ..config import check_accum, check_clip, check_loss
+        from ..config import check_accum, check_clip, check_loss, check_mix
         check_accum(cfg)
         check_loss(cfg)
+        check_mix(cfg)
         check_clip(cfg)
         self.cfg = cfg
         self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
@@ -284,7 +330,7 @@ class SingleStrategy(Strategy):
             from ..train.graph import GraphedTrainStep   # HIP-graph replay of the whole step
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B)
+                                            1.0 / B, mix=self.aug.mixing)
 
     def train_step(self, images, labels):
         self._fault_tick()
@@ -292,13 +338,14 @@ class SingleStrategy(Strategy):
         flip, off = self.aug(B)
         if self.graphed is not None and B == self.graphed.B and tuple(images.shape[1:3]) == self.graphed.images.shape[1:3]:
             return self.graphed(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
-                                flip, off).clone()
+                                flip, off, self.aug.mix(B, graphed=True)).clone()
         eng = self.engine
         acc = self.accum
+        mix = self.aug.mix(B)
         if acc is None:
-            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off).clone()
+            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=mix).clone()
         else:            # a micro-step: the update runs on every K-th call, from the mean over K batches
-            s = eng.forward_backward(images, labels, 1.0 / (B * acc.k), flip=flip, crop_offset=off).clone()
+            s = eng.forward_backward(images, labels, 1.0 / (B * acc.k), flip=flip, crop_offset=off, mix=mix).clone()
             acc.accumulate()
             if not acc.advance():
                 return s
@@ -366,7 +413,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
             from ..train.graph import GraphedTrainStep   # one rank: the whole step as one HIP graph
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B)
+                                            1.0 / B, mix=self.aug.mixing)
         # bucket_mb <= 0: autotune (Horovod's HOROVOD_AUTOTUNE analogue for the fusion threshold)
         self._tune = None
         mb = self.cfg.bucket_mb
@@ -452,7 +499,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
         if g is not None and images.shape[0] == g.B and tuple(images.shape[1:3]) == tuple(g.images.shape[1:3]):
             flip, off = self.aug(images.shape[0])
             return g(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
-                     flip, off).clone()
+                     flip, off, self.aug.mix(images.shape[0], graphed=True)).clone()
         s = self.compute_gradients(images, labels)
         if not self._update_due:       # (--accum-steps: micro-steps 1..K-1 only accumulate)
             return s
@@ -490,7 +537,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
         if acc is not None and cb is not None:
             cb = acc.wrap(cb)
         s = self.engine.forward_backward(images, labels, gscale, flip=flip, crop_offset=off, bucket_cb=cb,
-                                         buckets=bks).clone()
+                                         buckets=bks, mix=self.aug.mix(B)).clone()
         if acc is not None:
             if cb is None:
                 acc.accumulate()
@@ -785,7 +832,7 @@ class _LocalReplicas:
         for (eng, optim), d in zip(self.replicas, self.devices):
             with torch.cuda.device(d):
                 g = SegmentedStepGraphs(eng, optim, B, (H, W), 1.0 / global_batch, self.buckets,
-                                        image_dtype=parts[0][0].dtype)
+                                        image_dtype=parts[0][0].dtype, mix=self.augs[len(self.graphs)].mixing)
                 g.capture()
                 self.graphs.append(g)
         self.comm_streams = [torch.cuda.Stream(device=d) for d in self.devices]
@@ -855,7 +902,7 @@ class _LocalReplicas:
         for r, (g, d) in enumerate(zip(self.graphs, self.devices)):
             with torch.cuda.device(d):
                 flip, off = self.augs[r](B)
-                g.load(parts[r][0], parts[r][1], flip, off)
+                g.load(parts[r][0], parts[r][1], flip, off, self.augs[r].mix(B, graphed=True))
         P = self._plan(cur, amb)
         streams = P["comm"]
         tl = self.tl
@@ -1026,7 +1073,8 @@ class _LocalReplicas:
             if overlap:
                 cb = self._bucket_cb(i)
                 kw = dict(bucket_cb=accs[i].wrap(cb) if accs is not None else cb, buckets=self.buckets)
-            stats[i] = eng.forward_backward(im, lb, gscale, flip=flip, crop_offset=off, **kw).clone()
+            stats[i] = eng.forward_backward(im, lb, gscale, flip=flip, crop_offset=off,
+                                            mix=self.augs[i].mix(im.shape[0]), **kw).clone()
             if accs is not None:
                 if not overlap:
                     accs[i].accumulate()
@@ -1101,7 +1149,8 @@ class _LocalReplicas:
         with torch.cuda.device(d):
             flip, off = self.augs[0](im.shape[0])
             accs = self._accums()
-            s = eng.forward_backward(im, lb, 1.0 / (global_batch * self.accum_k), flip=flip, crop_offset=off).clone()
+            s = eng.forward_backward(im, lb, 1.0 / (global_batch * self.accum_k), flip=flip, crop_offset=off,
+                                     mix=self.augs[0].mix(im.shape[0])).clone()
             if accs is not None:
                 accs[0].accumulate()
                 if not accs[0].advance():
@@ -1118,10 +1167,10 @@ class _LocalReplicas:
         g = getattr(self, "_whole", None)
         if g is None or g.B != B or g.gscale != 1.0 / global_batch or tuple(g.images.shape[1:3]) != tuple(im.shape[1:3]):
             g = self._whole = GraphedTrainStep(eng, opt, B, tuple(im.shape[1:3]), 1.0 / global_batch,
-                                               image_dtype=im.dtype)
+                                               image_dtype=im.dtype, mix=self.augs[0].mixing)
         with torch.cuda.device(d):
             flip, off = self.augs[0](B)
-            return g(im, lb, flip, off).clone()
+            return g(im, lb, flip, off, self.augs[0].mix(B, graphed=True)).clone()
 
 
 class MirroredStrategy(Strategy):

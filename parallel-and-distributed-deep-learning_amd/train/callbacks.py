@@ -230,6 +230,10 @@ class JsonlLogger(Callback):
         rec["effective_global_batch"] = self.trainer.strategy.global_batch * k
         # (loss and val_loss above are the smoothed loss of this eps)
         rec["label_smoothing"] = float(getattr(self.trainer.cfg, "label_smoothing", 0.0))
+        # (under mixing, `accuracy` counts the argmax against the heavier of the two labels)
+        rec["mixup"] = float(getattr(self.trainer.cfg, "mixup", 0.0))
+        rec["cutmix"] = float(getattr(self.trainer.cfg, "cutmix", 0.0))
+        rec["mix_prob"] = float(getattr(self.trainer.cfg, "mix_prob", 1.0))
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)

@@ -7,7 +7,9 @@ replayed with a single launch, which removes host launch cost and inter-kernel g
 what keeps small per-GPU batches, e.g. the reference's 32, from being launch-bound).
 
 Everything that changes between steps lives in device memory the graph reads:
-  * inputs are copied into static buffers (images, labels, flip flags, crop offset),
+  * inputs are copied into static buffers (images, labels, flip flags, crop offset and, for a job
+    with --mixup / --cutmix, the per-image mix table: a batch that is not mixed loads the identity
+    table, which is bitwise the unmixed step, so one graph serves both),
   * the optimizer's step counter and learning rate are the device buffer `opt.hs`
     (train/optim.py), advanced by a kernel inside the graph; host LR changes are written to
     it between replays.
@@ -22,6 +24,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from .mix import identity_table
 
 
 # Capture in thread-local mode: under the default global mode any potentially unsafe HIP call
@@ -71,7 +74,7 @@ class GraphedTrainStep:
     parameter-server worker, whose update runs on the PS)."""
 
     def __init__(self, engine, optimizer, batch: int, image_hw: Tuple[int, int], gscale: float,
-                 image_dtype=torch.uint8, with_optimizer: bool = True):
+                 image_dtype=torch.uint8, with_optimizer: bool = True, mix: bool = False):
         if not engine.params.is_cuda:
             raise RuntimeError("GraphedTrainStep needs the GPU engine")
         self.engine, self.opt, self.B, self.gscale = engine, optimizer, batch, float(gscale)
@@ -86,6 +89,9 @@ class GraphedTrainStep:
             self.labels = torch.zeros(batch, dtype=torch.int64, device=dev)
         self.flip = torch.zeros(batch, dtype=torch.uint8, device=dev)
         self.crop = torch.zeros(2, dtype=torch.int32, device=dev)
+        # mix=True (a job with mixup / CutMix): the step is captured with the static mix table
+        self.mix = torch.from_numpy(identity_table(batch)).to(dev) if mix else None
+        self._mix_identity = True     # (mix holds the identity table: a table-less load needs no copy)
         self._flip_zero = True        # (flip holds zeros: a flip-less load needs no memset)
         self._crop_host = (0, 0)      # (the tuple crop currently in `crop`: unchanged -> no copy)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -93,13 +99,26 @@ class GraphedTrainStep:
 
     def _body(self):
         eng = self.engine
-        stats = eng.forward_backward(self.images, self.labels, self.gscale, flip=self.flip, crop_offset=self.crop)
+        stats = eng.forward_backward(self.images, self.labels, self.gscale, flip=self.flip, crop_offset=self.crop,
+                                     **self._mix_kw())
         if self.with_optimizer:
             self.opt.step()
             eng.after_update()
         return stats
 
-    def _load(self, images, labels, flip, crop_offset):
+    def _mix_kw(self):
+        return {} if self.mix is None else {"mix": self.mix}
+
+    def _load(self, images, labels, flip, crop_offset, mix=None):
+        if mix is None:
+            if not self._mix_identity:
+                self.mix.copy_(torch.from_numpy(identity_table(self.B)), non_blocking=True)
+                self._mix_identity = True
+        elif self.mix is None:
+            raise ValueError("a mix table for a step that was built without one (GraphedTrainStep(mix=True))")
+        else:
+            self.mix.copy_(mix[:self.B], non_blocking=True)
+            self._mix_identity = False
         self.images.copy_(images, non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
         if flip is None:
@@ -136,8 +155,8 @@ class GraphedTrainStep:
             self.opt._iterations = it    # the capture pass did not step (no setter: hs is current)
         self.graph = g
 
-    def __call__(self, images, labels, flip=None, crop_offset=(0, 0)):
-        self._load(images, labels, flip, crop_offset)
+    def __call__(self, images, labels, flip=None, crop_offset=(0, 0), mix=None):
+        self._load(images, labels, flip, crop_offset, mix)
         if self.graph is None:
             out = self._body()        # first call: eager (builds the engine's tables), then capture
             self.capture()
@@ -164,8 +183,8 @@ class SegmentedStepGraphs(GraphedTrainStep):
 
     def __init__(self, engine, optimizer, batch: int, image_hw: Tuple[int, int], gscale: float, buckets,
                  image_dtype=torch.uint8, two_stream: Optional[bool] = None, keep_graph: bool = False,
-                 probe=None):
-        super().__init__(engine, optimizer, batch, image_hw, gscale, image_dtype, with_optimizer=False)
+                 probe=None, mix: bool = False):
+        super().__init__(engine, optimizer, batch, image_hw, gscale, image_dtype, with_optimizer=False, mix=mix)
         self.buckets = list(buckets)
         self.segments = []
         self.side_segments = []          # deferred engines: segment k's weight-gradient graph (or None)
@@ -266,7 +285,8 @@ class SegmentedStepGraphs(GraphedTrainStep):
                     eng.begin_defer()
                 try:
                     self.stats = eng.forward_backward(self.images, self.labels, self.gscale, flip=self.flip,
-                                                      crop_offset=self.crop, bucket_cb=cut, buckets=self.buckets)
+                                                      crop_offset=self.crop, bucket_cb=cut, buckets=self.buckets,
+                                                      **self._mix_kw())
                     og = _new_graph(keep_graph=self.keep_graph)
                     live.append(og)
                     og.capture_begin(pool=pool[0], capture_error_mode=CAPTURE_MODE)
@@ -293,8 +313,8 @@ class SegmentedStepGraphs(GraphedTrainStep):
         self.side_segments = sides if deferred else [None] * nb
         self.opt_graph = og
 
-    def load(self, images, labels, flip=None, crop_offset=(0, 0)):
-        self._load(images, labels, flip, crop_offset)
+    def load(self, images, labels, flip=None, crop_offset=(0, 0), mix=None):
+        self._load(images, labels, flip, crop_offset, mix)
 
     def replay_segment(self, k: int):
         if self.segments[k] is not None:
