@@ -1066,6 +1066,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }
     return out;
   });
+  // The kernel launches of the calling thread's last conv_f32 / conv_f32_epi / wgrad_f32 call, one
+  // dict per launch (a split-K call: slices + combine):
+  //   kernel       "tile64" / "tile64_scalar" (conv_f32_kernel<VEC> / scalar gather), "big64" / "big128"
+  //                (conv_f32_big_kernel), "combine64" / "combine128" (conv_f32_splitk_kernel),
+  //                "wgrad64" / "wgrad64_scalar" (wgrad_f32_kernel), "wgrad128" (wgrad_f32_big_kernel)
+  //   slices       split-K slices (1: unsplit; the combine reports the slices it folds)
+  //   grid         workgroups launched
+  //   m_per_split  the weight gradients' GEMM rows per split (0 elsewhere)
+  m.def("conv_f32_last_launch", []() {
+    static const char* const kernel[] = {"tile64", "tile64_scalar", "big64", "big128", "combine64", "combine128",
+                                         "wgrad64", "wgrad64_scalar", "wgrad128"};
+    pddl::ConvF32LaunchInfo rec[2];
+    const int n = pddl::conv_f32_last_launch(rec, 2);
+    py::list out;
+    for (int i = 0; i < n; ++i) {
+      py::dict d;
+      d["kernel"] = kernel[rec[i].family];
+      d["slices"] = rec[i].slices;
+      d["grid"] = rec[i].grid;
+      d["m_per_split"] = rec[i].m_per_split;
+      out.append(d);
+    }
+    return out;
+  });
+  // (BN, tiles, slices, floats) of conv_f32's launcher under the current knobs: 128 x BN tiles (BN 0:
+  // the 64 x 64 kernels), split-K slices (1: unsplit) and the workspace floats it demands to split
+  m.def("conv_f32_splitk_plan", [](int M, int Cout, int K, int C, int RS) {
+    const pddl::ConvF32Plan pl = pddl::conv_f32_splitk_plan(M, Cout, K, C, RS);
+    return std::make_tuple(pl.BN, pl.tiles, pl.slices, (int64_t)pl.floats);
+  }, py::arg("M"), py::arg("Cout"), py::arg("K"), py::arg("C"), py::arg("RS"));
   // (train/graph.py: is the stream's current capture still empty?) (hip error, capture status, #deps)
   m.def("stream_capture_deps", [](int64_t stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

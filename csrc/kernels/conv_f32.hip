@@ -788,28 +788,55 @@ static const char* check_f32(const ConvF32Params& p) {
   return nullptr;
 }
 
+// The launches of this thread's last conv_f32_launch / wgrad_f32_launch (conv_f32_last_launch; kernels.h).
+static thread_local ConvF32LaunchInfo tl_f32_last[2];
+static thread_local int tl_f32_nlast = 0;
+static void f32_note(int family, int slices, long grid, int m_per_split) {
+  if (tl_f32_nlast < 2) tl_f32_last[tl_f32_nlast] = ConvF32LaunchInfo{family, slices, (int)grid, m_per_split};
+  ++tl_f32_nlast;
+}
+int conv_f32_last_launch(ConvF32LaunchInfo* out, int max) {
+  const int n = tl_f32_nlast < 2 ? tl_f32_nlast : 2;
+  for (int i = 0; i < n && i < max; ++i) out[i] = tl_f32_last[i];
+  return n;
+}
+
+// Tile width, tile count and split-K slices of a conv_f32_launch (BN 0: the 64 x 64 kernels).
+ConvF32Plan conv_f32_splitk_plan(int M, int Cout, int K, int C, int RS) {
+  ConvF32Plan pl{0, ((M + F_BM - 1) / F_BM) * ((Cout + F_BN - 1) / F_BN), 1, 0};
+  if (!(g_conv_f32_variant >= 1 && C % 16 == 0 && RS <= 32)) return pl;
+  const int mt = (M + G_BM - 1) / G_BM;
+  // 128 x 64 tiles unless forced: 4 workgroups per CU (36 KB of LDS, 76 VGPRs) against the wide
+  // tile's 3, equal or faster on every ResNet-50 layer (bench/f32.py, profiles/r4_fp32.txt)
+  pl.BN = g_conv_f32_variant == 2 ? 128 : 64;
+  pl.tiles = mt * ((Cout + pl.BN - 1) / pl.BN);
+  // split-K where the tiles leave CUs idle (small batches: b32 stage 5 is 104 tiles of a
+  // 288-step K loop on 256 CUs): slices aimed at 4 workgroups per CU, >= 8 K steps each, <= 8
+  const long T = pl.tiles, CU = num_cus(), KT = K / 16;
+  long ks = 1;
+  if (g_conv_f32_splitk > 0 && T < (long)g_conv_f32_sk_elig * CU) {
+    ks = ((long)g_conv_f32_splitk * CU + T - 1) / T;
+    if (ks > 8) ks = 8;
+    if (ks > KT / 8) ks = KT / 8;
+  }
+  if (ks >= 2) {
+    pl.slices = (int)ks;
+    pl.floats = T * ks * G_BM * pl.BN;
+  }
+  return pl;
+}
+
 const char* conv_f32_launch(ConvF32Params p, hipStream_t stream) {
+  tl_f32_nlast = 0;
   if (const char* e = check_f32(p)) return e;
   p.mg_howo = fdiv_magic(p.Ho * p.Wo);
   p.mg_wo = fdiv_magic(p.Wo);
-  if (g_conv_f32_variant >= 1 && p.C % 16 == 0 && p.R * p.S <= 32) {
-    const int mt = (p.M + G_BM - 1) / G_BM;
-    // 128 x 64 tiles unless forced: 4 workgroups per CU (36 KB of LDS, 76 VGPRs) against the wide
-    // tile's 3, equal or faster on every ResNet-50 layer (bench/f32.py, profiles/r4_fp32.txt)
-    const bool wide = g_conv_f32_variant == 2;
-    const int BN = wide ? 128 : 64;
-    const int T = mt * ((p.Cout + BN - 1) / BN);
-    // split-K where the tiles leave CUs idle (small batches: b32 stage 5 is 104 tiles of a
-    // 288-step K loop on 256 CUs): slices aimed at 4 workgroups per CU, >= 8 K steps each, <= 8
-    const long C = num_cus(), KT = p.K / 16;
-    long ks = 1;
-    if (g_conv_f32_splitk > 0 && T < (long)g_conv_f32_sk_elig * C) {
-      ks = ((long)g_conv_f32_splitk * C + T - 1) / T;
-      if (ks > 8) ks = 8;
-      if (ks > KT / 8) ks = KT / 8;
-    }
-    if (ks >= 2 && p.slab && p.slab_floats >= (long)T * ks * G_BM * BN) {
-      p.ksplit = (int)ks;
+  const ConvF32Plan pl = conv_f32_splitk_plan(p.M, p.Cout, p.K, p.C, p.R * p.S);
+  if (pl.BN) {
+    const bool wide = pl.BN == 128;
+    const int T = pl.tiles, ks = pl.slices;
+    if (ks >= 2 && p.slab && p.slab_floats >= pl.floats) {
+      p.ksplit = ks;
       if (wide) {
         hipLaunchKernelGGL(conv_f32_big_kernel<128>, dim3(T * ks), dim3(256), 0, stream, p);
         hipLaunchKernelGGL(conv_f32_splitk_kernel<128>, dim3(2 * T), dim3(256), 0, stream, p);
@@ -817,17 +844,21 @@ const char* conv_f32_launch(ConvF32Params p, hipStream_t stream) {
         hipLaunchKernelGGL(conv_f32_big_kernel<64>, dim3(T * ks), dim3(256), 0, stream, p);
         hipLaunchKernelGGL(conv_f32_splitk_kernel<64>, dim3(2 * T), dim3(256), 0, stream, p);
       }
+      f32_note(wide ? F32K_BIG128 : F32K_BIG64, ks, (long)T * ks, 0);
+      f32_note(wide ? F32K_COMBINE128 : F32K_COMBINE64, ks, 2L * T, 0);
     } else {
       p.ksplit = 1;
       if (wide) hipLaunchKernelGGL(conv_f32_big_kernel<128>, dim3(T), dim3(256), 0, stream, p);
       else hipLaunchKernelGGL(conv_f32_big_kernel<64>, dim3(T), dim3(256), 0, stream, p);
+      f32_note(wide ? F32K_BIG128 : F32K_BIG64, 1, T, 0);
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }
-  const int grid = ((p.M + F_BM - 1) / F_BM) * ((p.Cout + F_BN - 1) / F_BN);
+  const int grid = pl.tiles;
   if (p.C % 4 == 0) hipLaunchKernelGGL(conv_f32_kernel<true>, dim3(grid), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(conv_f32_kernel<false>, dim3(grid), dim3(256), 0, stream, p);
+  f32_note(p.C % 4 == 0 ? F32K_TILE64 : F32K_TILE64_SCALAR, 1, grid, 0);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
@@ -842,6 +873,7 @@ const char* conv_f32_launch(ConvF32Params p, hipStream_t stream) {
 // 128-wide ones now share the CUs with the data-gradient chain.
 int g_wgrad_f32_wpc[2] = {16, 3};
 const char* wgrad_f32_launch(ConvF32Params p, hipStream_t stream) {
+  tl_f32_nlast = 0;
   if (const char* e = check_f32(p)) return e;
   p.mg_howo = fdiv_magic(p.Ho * p.Wo);
   p.mg_wo = fdiv_magic(p.Wo);
@@ -864,11 +896,13 @@ const char* wgrad_f32_launch(ConvF32Params p, hipStream_t stream) {
     const int bmps = ((p.M + bs - 1) / bs + 15) / 16 * 16;
     bs = (p.M + bmps - 1) / bmps;
     hipLaunchKernelGGL(wgrad_f32_big_kernel, dim3(bt * bs), dim3(256), 0, stream, p, bmps);
+    f32_note(F32K_WGRAD128, 1, (long)bt * bs, bmps);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }
   if (p.C % 4 == 0) hipLaunchKernelGGL(wgrad_f32_kernel<true>, dim3(ntiles * splits), dim3(256), 0, stream, p, mps);
   else hipLaunchKernelGGL(wgrad_f32_kernel<false>, dim3(ntiles * splits), dim3(256), 0, stream, p, mps);
+  f32_note(p.C % 4 == 0 ? F32K_WGRAD64 : F32K_WGRAD64_SCALAR, 1, (long)ntiles * splits, mps);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }

@@ -158,6 +158,27 @@ enum { F32_EPI_PLAIN = 0, F32_EPI_FWD = 1, F32_EPI_DGRAD = 2 };
 const char* conv_f32_launch(ConvF32Params p, hipStream_t stream);
 extern int g_conv_f32_variant, g_conv_f32_splitk, g_conv_f32_sk_elig;   // 0: 64 x 64 register-staged fp32 kernels; 1: LDS-DMA 128 x {64, 128} by model (default); 2: 128 x 128; 3: 128 x 64
 const char* wgrad_f32_launch(ConvF32Params p, hipStream_t stream);
+// What the calling thread's last conv_f32_launch / wgrad_f32_launch launched, one record per kernel
+// launch (tests: did the forced kernel really run?).  A split-K call leaves two.
+enum ConvF32Family {
+  F32K_TILE64 = 0, F32K_TILE64_SCALAR = 1,     // conv_f32_kernel<VEC = true / false>
+  F32K_BIG64 = 2, F32K_BIG128 = 3,             // conv_f32_big_kernel<64 / 128>
+  F32K_COMBINE64 = 4, F32K_COMBINE128 = 5,     // conv_f32_splitk_kernel<64 / 128>
+  F32K_WGRAD64 = 6, F32K_WGRAD64_SCALAR = 7,   // wgrad_f32_kernel<VEC = true / false>
+  F32K_WGRAD128 = 8                            // wgrad_f32_big_kernel
+};
+struct ConvF32LaunchInfo {
+  int family;          // ConvF32Family
+  int slices;          // split-K slices (1: unsplit; the combine reports the slices it folds)
+  int grid;            // workgroups launched
+  int m_per_split;     // weight gradients: GEMM rows per workgroup split (else 0)
+};
+int conv_f32_last_launch(ConvF32LaunchInfo* out, int max);   // -> number of records (at most max copied)
+// The tiling conv_f32_launch takes for a problem under the current knobs: BN 64 / 128 = the
+// 128 x BN LDS-DMA tiles (0: the 64 x 64 kernels), their count, the split-K slices (1: unsplit) and
+// the workspace floats the launcher demands to split (tiles * slices * 128 * BN; 0: no split).
+struct ConvF32Plan { int BN, tiles, slices; long floats; };
+ConvF32Plan conv_f32_splitk_plan(int M, int Cout, int K, int C, int RS);
 // fp32 elementwise kernels of the fp32 engine (f32.hip)
 const char* maxpool_fwd_f32_launch(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int Ho, int Wo,
                                    hipStream_t s);

@@ -6,13 +6,15 @@ distances in units in the last place, `table` packs a launch table the way the e
 `pack_bits`, `pool_ref` and `pool_bwd_ref` are the plain references of the ReLU bit masks and of
 the 3x3 / stride-2 max-pool that several kernels fuse.
 
-The matrix-core kernel tests (test_gpu_fused_kernels.py, test_gpu_gemm_kernels.py) share their
-host-generated inputs (`gen`, `tern`, `ints`, `pick`, `randn`, `bn`) and their two checks:
-`check_exact` (small integers: bit for bit against fp64, `precond` asserting on the reference that
-fp32 accumulation is exact) and `check_real` (a per-element error bound), `check_bits` /
-`untouched` for the ReLU bit outputs.
+The matrix-core kernel tests (test_gpu_fused_kernels.py, test_gpu_gemm_kernels.py,
+test_gpu_conv_f32_kernels.py) share their host-generated inputs (`gen`, `tern`, `ints`, `pick`,
+`randn`, `bn`) and their two checks: `check_exact` (small integers: bit for bit against fp64,
+`precond` asserting on the reference that fp32 accumulation is exact) and `check_real` (a
+per-element error bound), `check_bits` / `untouched` for the ReLU bit outputs; `gather` is the
+fp64 im2col of the implicit GEMMs and `guards_only` the check of a split-K workspace.
 """
 import torch
+import torch.nn.functional as F
 
 dev = "cuda"
 SENT16 = 0x7FA5          # bf16 sentinel: a NaN no kernel here produces
@@ -192,6 +194,22 @@ def untouched(bt, what):
 
 def nothing(n):
     return torch.zeros(n, dtype=torch.bool, device=dev)
+
+
+def guards_only(o, what):
+    """A workspace: whatever of it was written, the guards around it were not."""
+    o.check(what, ~is_sent(o.t))
+
+
+def gather(a, H, W, R, S, stride, pad, Ho, Wo):
+    """The gathered A matrix by a scan over the taps, fp64: [N, H, W, C] -> [N Ho Wo, R S C] with
+    k = (r S + s) C + c, zero outside the image."""
+    n, C = a.shape[0], a.shape[-1]
+    eh, ew = max(0, (Ho - 1) * stride + R - pad - H), max(0, (Wo - 1) * stride + S - pad - W)
+    xp = F.pad(a.double().view(n, H, W, C), (0, 0, pad, ew, pad, eh))
+    taps = [xp[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
+            for r in range(R) for s in range(S)]
+    return torch.stack(taps, 3).reshape(n * Ho * Wo, R * S * C)
 
 
 def pool_ref(x):

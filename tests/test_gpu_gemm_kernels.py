@@ -35,10 +35,9 @@ from types import SimpleNamespace as NS
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from kernel_checks import (BF, F32, PRECOND, ByteOut, Out, bn, check, dev, gen, ints, is_sent, pack_bits, precond,
-                           randn, tern, untouched)
+from kernel_checks import (BF, F32, PRECOND, ByteOut, Out, bn, check, dev, gather, gen, guards_only, ints, pack_bits,
+                           precond, randn, tern, untouched)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,17 +83,6 @@ def _report_preconditions():
 
 
 # ---------------------------------------------------------------------------- references
-def gather(a, H, W, R, S, stride, pad, Ho, Wo):
-    """The gathered A matrix by a scan over the taps, fp64: [N, H, W, C] -> [N Ho Wo, R S C] with
-    k = (r S + s) C + c, zero outside the image."""
-    n, C = a.shape[0], a.shape[-1]
-    eh, ew = max(0, (Ho - 1) * stride + R - pad - H), max(0, (Wo - 1) * stride + S - pad - W)
-    xp = F.pad(a.double().view(n, H, W, C), (0, 0, pad, ew, pad, eh))
-    taps = [xp[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
-            for r in range(R) for s in range(S)]
-    return torch.stack(taps, 3).reshape(n * Ho * Wo, R * S * C)
-
-
 def gathered(a1, a2, geom):
     """A of one or two sources; the second at its own H2 x W2 and stride2 = ceil(H2 / Ho) (1x1)."""
     H, W, R, S, stride, pad, Ho, Wo = geom
@@ -161,10 +149,6 @@ class ByteRows:
         assert bool((full[:, self.v.shape[1]:] == 0xA5).all()), f"{what}: bits pad written"
         want = pack_bits(stored.contiguous()).view(stored.shape[0], -1)
         assert torch.equal(self.v, want), f"{what}: bits != packed (stored output > 0)"
-
-
-def guards_only(o, what):
-    o.check(what, ~is_sent(o.t))
 
 
 def launched(nat, expect, what):
