@@ -508,15 +508,22 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || PRE) ? 1 : 2) bwd1x1_kern
 
 // Launch geometry: (workgroups, pairs).  NW = 4 (CO 256): two per CU, one per tile column
 // block; NW = 8 (CO 512, CI 128): one per CU, as pairs (a multiple of 8 pairs: the XCD pairing).
+int g_bwd1x1_grid = 0;   // test knob: cap on the workgroup (CO 512: pair) count (0: off), like c64_grid,
+                         // so that a small problem makes one workgroup walk several tiles
 static void bwd1x1_geom(int M, int CO, int CI, bool dual, int* grid, int* np) {
   const long T = (M + B1_MT - 1) / B1_MT;
   if (CO == 256) {
-    const long G = (dual ? 1L : 2L) * num_cus();   // (dual: eight waves, one workgroup per CU)
+    long G = (dual ? 1L : 2L) * num_cus();   // (dual: eight waves, one workgroup per CU)
+    if (g_bwd1x1_grid > 0 && g_bwd1x1_grid < G) G = g_bwd1x1_grid;
     *np = *grid = (int)(T < G ? T : G);
     return;
   }
   long P = (num_cus() / 2) / 8 * 8;
   if (P < 8) P = 8;
+  if (g_bwd1x1_grid > 0) {   // (the pair count stays a multiple of 8)
+    const long c = g_bwd1x1_grid / 8 * 8 > 8 ? g_bwd1x1_grid / 8 * 8 : 8;
+    if (c < P) P = c;
+  }
   *np = (int)P;
   *grid = (int)(P * (CI / 64));
 }

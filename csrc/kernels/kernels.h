@@ -129,6 +129,7 @@ struct Bwd1x1Params {
 const char* bwd1x1_launch(const Bwd1x1Params& p, hipStream_t stream);
 // (dual: the rows a dual-form launch writes -- one 8-wave workgroup per CU)
 int bwd1x1_partial_rows(int M, int CO, int CI, bool dual = false);
+extern int g_bwd1x1_grid;              // test cap on the workgroup (CO 512: pair) count, 0 off
 
 // ---- fp32 convolution on the fp32 matrix cores (conv_f32.hip): the reference-precision path ----
 struct ConvF32Params {

@@ -15,6 +15,18 @@ their tiling can go wrong.
   bwd1x1       plain (both channel pairs, M around the tile, padded wd / dw rows), stride-2
                (odd and even sides; `out` owned at the grid pixels only, not pre-zeroed) and
                pre form (downstream outputs against a reference from the kernel's own gx)
+  ..._multitile  every form with its workgroups capped (bwd1x1_grid: 1 and 3 workgroups, 8 pairs
+               of the (512, 128) form), so that one workgroup walks 2-6 tiles of a few hundred
+               rows: both LDS buffers, even and odd parity at the end, a full and a 1-row last
+               tile, workgroups that end on different buffers, the prefetched ReLU bits, the
+               staging written over the g images under the next tile's DMA, dW summed across
+               tiles, the empty last DMA; stride-2 tiles that begin inside an image and span two
+  ..._real_grid  plain (both channel pairs) and dual at the production grid, M = 128 W + 37 for W
+               workgroups / pairs: every one runs 2-3 tiles at stride W, the last tile 37 rows
+  ..._dual     the dual form element by element, M = 1, 65, 300 and the capped shapes: wd2 a
+               column slice and dw / dw2 two ranges of one 320-float-row tensor (the rest stays
+               sentinel), gx given and gx=None (out / out_s bit-identical, a gx buffer not
+               passed untouched), every partial row written, the column-sum rows of waves 4-7 zero
 
 Every bf16 / fp32 output is an `Out` (sentinel NaN inside guards), every bits / argmax output a
 `ByteOut`; accumulators start nonzero.  Each case runs twice:
@@ -441,6 +453,77 @@ def b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what):
     check(kind, dw.t.view(CO, ld_dw)[:, :CI], r.dw, r.dw_mag, M, what + " dw", rounded=False)
 
 
+def b1_precond(kernel, r):
+    """Exact kind: every sum |a||b| (|dw0| + sum_m |g||x| included) below 2^24, `out` integers of
+    magnitude <= 256, and each column's sum_m |out| below 2^24 (the fp32 column sums are exact in
+    any order, however many tiles and workgroups they are folded over)."""
+    precond(kernel, torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1), r.out.abs().sum(0)]), r.out)
+
+
+def b1_dw(CO, CI, dw0, padded):
+    """dW preloaded with dw0; padded: rows of CI + 4 floats whose pad is not the kernel's (stays sentinel)."""
+    ld_dw = CI + 4 if padded else CI
+    dw = Out(CO * ld_dw, F32)
+    dw.t.view(CO, ld_dw)[:, :CI] = dw0
+    return dw, ld_dw, (torch.arange(CO * ld_dw, device=dev) % ld_dw) < CI
+
+
+def b1_rows(nat, what, M, CO, CI, want, dual=False):
+    """The partial rows the launcher reports; `want`: the rows of the capped / production grid
+    (did the geometry under test really run?)."""
+    rows = nat.bwd1x1_partial_rows(M, CO, CI, dual)
+    if want is not None:
+        assert rows == want, f"{what}: {rows} partial rows, {want} expected from the grid under test"
+    return rows
+
+
+def b1_grid(nat, CO, CI, dual=False):
+    """(W, M, rows) of the real-grid cases: W the workgroups (pairs) of a large problem, M = 128 W +
+    37 rows -- 2 W + 1 tiles, so every workgroup runs 2-3 tiles at stride W."""
+    nw = 4 if CO == 256 and not dual else 8
+    rows = nat.bwd1x1_partial_rows(1 << 20, CO, CI, dual)
+    return rows // nw, 64 * 2 * (rows // nw) + 37, rows
+
+
+def test_bwd1x1_grid_knob(knob):
+    """bwd1x1_grid = 0 leaves the launch geometry as it is (2 workgroups per CU, dual 1, CU / 2
+    pairs in multiples of 8, never more workgroups than tiles of the 256 forms); v > 0 caps the
+    workgroups, the pairs in multiples of 8 and at least 8; v < 0 is refused."""
+    nat = N()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    pairs = max(8, cus // 2 // 8 * 8)
+    for cap in (0, 1, 3, 8, 20, 1 << 20):
+        knob("bwd1x1_grid", cap)
+        for M in (1, 64, 65, 477, 64 * 3 * cus + 1):
+            T = (M + 63) // 64
+            assert nat.bwd1x1_partial_rows(M, 256, 64) == min(T, 2 * cus, cap or T) * 4, (cap, M)
+            assert nat.bwd1x1_partial_rows(M, 256, 64, True) == min(T, cus, cap or T) * 8, (cap, M)
+            assert nat.bwd1x1_partial_rows(M, 512, 128) == (min(pairs, max(8, cap // 8 * 8)) if cap else pairs) * 8, (cap, M)
+    knob("bwd1x1_grid", 3)
+    with pytest.raises(RuntimeError, match="bwd1x1_grid"):
+        nat.set_variant("bwd1x1_grid", -1)
+    assert nat.bwd1x1_partial_rows(1 << 20, 256, 64) == 3 * 4       # (the refused value changed nothing)
+
+
+def b1_plain(nat, CO, CI, M, padded, kind, want_rows=None):
+    exact = kind == "exact"
+    ld_wd = CO + 8 if padded else CO
+    what = f"bwd1x1 ({CO},{CI}) M={M} padded={padded} rows={want_rows} {kind}"
+    gy, x, wd, dw0, keep = b1_inputs(gen(5000 + CO + 2 * M + exact), M, CO, CI, exact, ld_wd)
+    r = b1_refs(gy, x, wd, dw0, keep)
+    if exact:
+        b1_precond("bwd1x1", r)
+    rows = b1_rows(nat, what, M, CO, CI, want_rows)
+    out, cs = Out(M * CI, BF), Out(rows * CI, F32)
+    dw, ld_dw, dw_owned = b1_dw(CO, CI, dw0, padded)
+    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(M, CI // 8), out.t.view(M, CI), cs.t, dw.t.view(CO, ld_dw))
+    out.check(what + " out")
+    cs.check(what + " colsum")
+    dw.check(what + " dw", dw_owned)
+    check(kind, out.t, r.out, r.out_mag, CO, what + " out")
+    b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what)
+
+
 B1_CASES = [(co, ci, M, False) for co, ci in ((256, 64), (512, 128)) for M in (1, 63, 64, 65, 257)] + \
            [(256, 64, 65, True), (512, 128, 65, True)]
 
@@ -448,40 +531,42 @@ B1_CASES = [(co, ci, M, False) for co, ci in ((256, 64), (512, 128)) for M in (1
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("CO,CI,M,padded", B1_CASES, ids=str)
 def test_bwd1x1_plain(CO, CI, M, padded, kind):
-    nat = N()
-    exact = kind == "exact"
-    ld_wd, ld_dw = (CO + 8, CI + 4) if padded else (CO, CI)
-    what = f"bwd1x1 ({CO},{CI}) M={M} padded={padded} {kind}"
-    gy, x, wd, dw0, keep = b1_inputs(gen(5000 + CO + 2 * M + exact), M, CO, CI, exact, ld_wd)
-    r = b1_refs(gy, x, wd, dw0, keep)
-    if exact:
-        precond("bwd1x1", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
-    rows = nat.bwd1x1_partial_rows(M, CO, CI)
-    out, cs = Out(M * CI, BF), Out(rows * CI, F32)
-    if padded:      # the pad columns of each dw row are not the kernel's: they stay sentinel
-        dw = Out(CO * ld_dw, F32)
-        dw.t.view(CO, ld_dw)[:, :CI] = dw0
-    else:
-        dw = Out(CO * CI, F32, start=dw0)
-    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(M, CI // 8), out.t.view(M, CI), cs.t, dw.t.view(CO, ld_dw))
-    out.check(what + " out")
-    cs.check(what + " colsum")
-    dw.check(what + " dw", (torch.arange(CO * ld_dw, device=dev) % ld_dw) < CI)
-    check(kind, out.t, r.out, r.out_mag, CO, what + " out")
-    b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what)
+    b1_plain(N(), CO, CI, M, padded, kind)
+
+
+# (CO, CI, cap, M, padded): one workgroup over 6 / 4 / 4 tiles (a 13-row, a full and a 1-row last tile);
+# 8 tiles over 3 workgroups (3, 3, 2: they end on different buffers); 20 and 16 tiles over 8 pairs
+# (3, 3, 3, 3, 2, 2, 2, 2 and 2 each, both halves of every pair)
+B1_MULTI = [(256, 64, 1, 333, True), (256, 64, 1, 256, False), (256, 64, 1, 193, False), (256, 64, 3, 477, False),
+            (512, 128, 8, 1221, True), (512, 128, 8, 1024, False)]
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("B,Hf,Wf", [(1, 7, 5), (2, 13, 11), (1, 6, 8), (2, 12, 10)], ids=str)
+@pytest.mark.parametrize("CO,CI,cap,M,padded", B1_MULTI, ids=str)
+def test_bwd1x1_plain_multitile(knob, CO, CI, cap, M, padded, kind):
+    """The persistent tile loop: with the workgroups capped one of them walks several tiles, so the
+    two stage buffers alternate, the ReLU bits of the next tile are prefetched and rotated, the
+    dgrad staging overwrites the g images under the next tile's DMA and dW is summed over tiles."""
+    knob("bwd1x1_grid", cap)
+    b1_plain(N(), CO, CI, M, padded, kind, want_rows=cap * 4 if CO == 256 else 8 * 8)
+
+
+@pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("CO,CI", [(256, 64), (512, 128)])
-def test_bwd1x1_stride2(CO, CI, B, Hf, Wf, kind):
+def test_bwd1x1_plain_real_grid(CO, CI, kind):
+    """The production grid (knob at 0) with 2-3 tiles per workgroup (pair) at stride W."""
+    nat = N()
+    _, M, rows = b1_grid(nat, CO, CI)
+    b1_plain(nat, CO, CI, M, False, kind, want_rows=rows)
+
+
+def b1_stride2(nat, CO, CI, B, Hf, Wf, kind, padded=False, want_rows=None):
     """The gradient lives on the stride-2 grid; `out` is full resolution, starts as sentinels and
     must be written at the grid pixels only; `out2` is the compact copy."""
-    nat = N()
     exact = kind == "exact"
     Hc, Wc = (Hf + 1) // 2, (Wf + 1) // 2
     M = B * Hc * Wc
-    what = f"bwd1x1 stride-2 ({CO},{CI}) B={B} {Hf}x{Wf} {kind}"
+    what = f"bwd1x1 stride-2 ({CO},{CI}) B={B} {Hf}x{Wf} padded={padded} rows={want_rows} {kind}"
     g = gen(6000 + CO + 16 * Hf + B + exact)
     gy, _, wd, dw0, _ = b1_inputs(g, M, CO, CI, exact)
     gy = gy.view(B, Hc, Wc, CO)
@@ -489,30 +574,50 @@ def test_bwd1x1_stride2(CO, CI, B, Hf, Wf, kind):
     keep = randn(g, B, Hf, Wf, CI)
     r = b1_refs(gy, x[:, ::2, ::2], wd, dw0, keep[:, ::2, ::2])
     if exact:
-        precond("bwd1x1 stride-2", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
-    rows = nat.bwd1x1_partial_rows(M, CO, CI)
-    out, out2, cs, dw = Out(B * Hf * Wf * CI, BF), Out(M * CI, BF), Out(rows * CI, F32), Out(CO * CI, F32, start=dw0)
-    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(B, Hf, Wf, CI // 8), out.t.view(B, Hf, Wf, CI), cs.t, dw.t.view(CO, CI),
-               out2.t.view(B, Hc, Wc, CI))
+        b1_precond("bwd1x1 stride-2", r)
+    rows = b1_rows(nat, what, M, CO, CI, want_rows)
+    out, out2, cs = Out(B * Hf * Wf * CI, BF), Out(M * CI, BF), Out(rows * CI, F32)
+    dw, ld_dw, dw_owned = b1_dw(CO, CI, dw0, padded)
+    nat.bwd1x1(gy, x, wd, pack_bits(keep).view(B, Hf, Wf, CI // 8), out.t.view(B, Hf, Wf, CI), cs.t,
+               dw.t.view(CO, ld_dw), out2.t.view(B, Hc, Wc, CI))
     on_grid = torch.zeros(B, Hf, Wf, CI, dtype=torch.bool, device=dev)
     on_grid[:, ::2, ::2] = True
     out.check(what + " out", on_grid.reshape(-1))
     out2.check(what + " out2")
     cs.check(what + " colsum")
-    dw.check(what + " dw")
+    dw.check(what + " dw", dw_owned)
     check(kind, out.t.view(B, Hf, Wf, CI)[:, ::2, ::2].contiguous(), r.out, r.out_mag, CO, what + " out")
     check(kind, out2.t, r.out, r.out_mag, CO, what + " out2")
-    b1_check_sums(kind, cs, rows, CI, dw, CI, r, M, CO, what)
+    b1_check_sums(kind, cs, rows, CI, dw, ld_dw, r, M, CO, what)
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("M", [1, 65, 300])
-def test_bwd1x1_pre(M, kind):
+@pytest.mark.parametrize("B,Hf,Wf", [(1, 7, 5), (2, 13, 11), (1, 6, 8), (2, 12, 10)], ids=str)
+@pytest.mark.parametrize("CO,CI", [(256, 64), (512, 128)])
+def test_bwd1x1_stride2(CO, CI, B, Hf, Wf, kind):
+    b1_stride2(N(), CO, CI, B, Hf, Wf, kind)
+
+
+# (CO, CI, cap, B, Hf, Wf, padded): 121-pixel images (M = 363: 6 tiles, each but the first beginning inside
+# an image, two spanning two) over 1 and 3 workgroups; 132-pixel images (M = 660: 11 tiles, four spanning
+# two images) over 8 pairs, three of which run 2 tiles and five 1
+B1_S2_MULTI = [(256, 64, 1, 3, 21, 21, False), (256, 64, 3, 3, 21, 21, True), (512, 128, 8, 5, 23, 21, True)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("CO,CI,cap,B,Hf,Wf,padded", B1_S2_MULTI, ids=str)
+def test_bwd1x1_stride2_multitile(knob, CO, CI, cap, B, Hf, Wf, padded, kind):
+    """From the second tile on the x descriptor is rebased at the tile's first image (n_first) and
+    the next tile's bits are prefetched through the compact-to-full row map."""
+    knob("bwd1x1_grid", cap)
+    b1_stride2(N(), CO, CI, B, Hf, Wf, kind, padded, want_rows=cap * 4 if CO == 256 else 8 * 8)
+
+
+def b1_pre(nat, M, kind, padded=False, want_rows=None):
     """gx = bit(gmask) * (g1 . w1d^T + g) with its column sums against fp64; then the plain
     form's outputs against a reference that starts from the kernel's own (rounded) gx."""
-    nat = N()
     exact = kind == "exact"
-    what = f"bwd1x1 pre M={M} {kind}"
+    what = f"bwd1x1 pre M={M} padded={padded} rows={want_rows} {kind}"
     g = gen(7000 + 2 * M + exact)
     if exact:
         g1, w1d, add = tern(g, M, 64, p=0.125), ints(g, -1, 1, 256, 64), ints(g, -2, 2, M, 256)
@@ -526,19 +631,124 @@ def test_bwd1x1_pre(M, kind):
     gx_ref = (g1.double() @ w1d.double().t() + add.double()) * on
     gx_mag = (g1.double().abs() @ w1d.double().abs().t() + add.double().abs()) * on
     if exact:
-        precond("bwd1x1 pre gx", gx_mag, gx_ref)
-    rows = nat.bwd1x1_partial_rows(M, 256, 64)
+        precond("bwd1x1 pre gx", torch.cat([gx_mag.reshape(-1), gx_ref.abs().sum(0)]), gx_ref)
+    rows = b1_rows(nat, what, M, 256, 64, want_rows)
     gx, csx = Out(M * 256, BF), Out(rows * 256, F32)
-    out, cs, dw = Out(M * 64, BF), Out(rows * 64, F32), Out(256 * 64, F32, start=dw0)
-    nat.bwd1x1(add, x, wd, pack_bits(keep).view(M, 8), out.t.view(M, 64), cs.t, dw.t.view(256, 64),
+    out, cs = Out(M * 64, BF), Out(rows * 64, F32)
+    dw, ld_dw, dw_owned = b1_dw(256, 64, dw0, padded)
+    nat.bwd1x1(add, x, wd, pack_bits(keep).view(M, 8), out.t.view(M, 64), cs.t, dw.t.view(256, ld_dw),
                g1=g1, w1d=w1d, gmask=pack_bits(ox).view(M, 32), gx=gx.t.view(M, 256), colsum_gx=csx.t)
-    for o, name in ((gx, "gx"), (csx, "colsum_gx"), (out, "out"), (cs, "colsum"), (dw, "dw")):
+    for o, name in ((gx, "gx"), (csx, "colsum_gx"), (out, "out"), (cs, "colsum")):
         o.check(f"{what} {name}")
+    dw.check(what + " dw", dw_owned)
     check(kind, gx.t, gx_ref, gx_mag, 64, what + " gx")
     fold = csx.t.view(rows, 256).double().sum(0)
     check(kind, fold, gx_ref.sum(0), gx_mag.sum(0), 64 + M + 2, what + " colsum_gx", rounded=False)
     r = b1_refs(gx.t.view(M, 256), x, wd, dw0, keep)
     if exact:
-        precond("bwd1x1 pre", torch.cat([r.out_mag.reshape(-1), r.dw_mag.reshape(-1)]), r.out)
+        b1_precond("bwd1x1 pre", r)
     check(kind, out.t, r.out, r.out_mag, 256, what + " out")
-    b1_check_sums(kind, cs, rows, 64, dw, 64, r, M, 256, what)
+    b1_check_sums(kind, cs, rows, 64, dw, ld_dw, r, M, 256, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("M", [1, 65, 300])
+def test_bwd1x1_pre(M, kind):
+    b1_pre(N(), M, kind)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("M,padded", [(333, False), (477, True)], ids=str)
+@pytest.mark.parametrize("cap", [1, 3])
+def test_bwd1x1_pre_multitile(knob, cap, M, padded, kind):
+    """g is overwritten in place in both stage buffers, gx stored from every tile and its column
+    sums carried in registers across the workgroup's tiles."""
+    knob("bwd1x1_grid", cap)
+    b1_pre(N(), M, kind, padded, want_rows=cap * 4)
+
+
+# (M, cap): less than a tile, a 1-row second tile, a ragged 5th; 6 and 8 tiles over 1 and 3 workgroups;
+# "grid": the production grid with 2-3 tiles per workgroup
+B1_DUAL = [(1, 0), (65, 0), (300, 0), (333, 1), (477, 1), (333, 3), (477, 3), ("grid", 0)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("M,cap", B1_DUAL, ids=str)
+def test_bwd1x1_dual(knob, M, cap, kind):
+    """The dual form as the engine launches it (wd2 a column slice with 320-element rows, dw and dw2
+    two 64-column ranges of one [256][320] tensor), once with gx and once without.  gx and its
+    column sums against fp64; out / out_s / dw / dw2 / column sums against fp64 from the fp64 g
+    (exact: g is an integer of magnitude <= 256, so the bf16 tile holds it exactly) or from the
+    kernel's own stored gx (real: the tile is that bf16 g).  Without gx: out and out_s bit-identical
+    (each tile's GEMMs run in a fixed order; the gx branch only stores), the sums and weight
+    gradients within the same bounds, a gx buffer that is not passed untouched."""
+    nat = N()
+    exact = kind == "exact"
+    W, Mg, full = b1_grid(nat, 256, 64, True)
+    if M == "grid":
+        M, want = Mg, full
+    else:
+        want = (cap if cap else min((M + 63) // 64, W)) * 8
+    what = f"bwd1x1 dual M={M} cap={cap} {kind}"
+    knob("bwd1x1_grid", cap)
+    rows = b1_rows(nat, what, M, 256, 64, want, dual=True)
+    g = gen(8000 + 2 * M + exact)
+    wd_all = torch.full((64, 320), float("inf"), dtype=BF, device=dev)      # columns 0-63 are never read
+    if exact:
+        g1, w1d, add = tern(g, M, 64, p=0.125), ints(g, -1, 1, 256, 64), ints(g, -2, 2, M, 256)
+        x2, w2, dw20 = tern(g, M, 64), ints(g, -2, 2, 64, 256), ints(g, -9, 9, 256, 64, dtype=F32) + 0.5
+    else:
+        g1, w1d, add = randn(g, M, 64), randn(g, 256, 64, scale=0.05), randn(g, M, 256)
+        x2, w2, dw20 = torch.relu(randn(g, M, 64)), randn(g, 64, 256, scale=0.05), randn(g, 256, 64, dtype=F32)
+    ox = randn(g, M, 256)
+    _, x, wd, dw0, keep = b1_inputs(g, M, 256, 64, exact)
+    if exact:       # sparse weights keep |out|, |out_s| <= 256
+        wd = (wd.float() * (torch.rand(64, 256, generator=g) < 0.125).to(dev)).to(BF)
+        w2 = (w2.float() * (torch.rand(64, 256, generator=g) < 0.125).to(dev)).to(BF)
+    wd_all[:, 64:] = w2
+    wd2 = wd_all[:, 64:]
+    on = ox.double() > 0
+    gx_ref = (g1.double() @ w1d.double().t() + add.double()) * on
+    gx_mag = (g1.double().abs() @ w1d.double().abs().t() + add.double().abs()) * on
+    if exact:
+        precond("bwd1x1 dual gx", torch.cat([gx_mag.reshape(-1), gx_ref.abs().sum(0)]), gx_ref)
+    bits, gmask = pack_bits(keep).view(M, 8), pack_bits(ox).view(M, 32)
+    dw_owned = (torch.arange(256 * 320, device=dev) % 320) < 128
+
+    def launch(gx):
+        o = NS(out=Out(M * 64, BF), out_s=Out(M * 64, BF), cs=Out(rows * 64, F32), csx=Out(rows * 256, F32),
+               dwa=Out(256 * 320, F32))
+        dwa = o.dwa.t.view(256, 320)
+        dwa[:, :64], dwa[:, 64:128] = dw0, dw20
+        nat.bwd1x1(add, x, wd, bits, o.out.t.view(M, 64), o.cs.t, dwa[:, :64], g1=g1, w1d=w1d, gmask=gmask, gx=gx,
+                   colsum_gx=o.csx.t, x2=x2, wd2=wd2, out_s=o.out_s.t.view(M, 64), dw2=dwa[:, 64:128])
+        return o
+
+    gx = Out(M * 256, BF)
+    a = launch(gx.t.view(M, 256))
+    gx.check(what + " gx")
+    check(kind, gx.t, gx_ref, gx_mag, 64, what + " gx")
+    gsrc = gx_ref if exact else gx.t.view(M, 256)
+    r = b1_refs(gsrc, x, wd, dw0, keep)
+    r2 = b1_refs(gsrc, x2, wd2, dw20, torch.ones(M, 64, device=dev))         # the shortcut half: no mask
+    if exact:
+        b1_precond("bwd1x1 dual", r)
+        b1_precond("bwd1x1 dual shortcut", r2)
+    gx_none = Out(M * 256, BF)
+    b = launch(None)
+    gx_none.check(what + " gx not passed", nothing(M * 256))
+    for o, tag in ((a, what + " with gx"), (b, what + " gx=None")):
+        for t, name in ((o.out, "out"), (o.out_s, "out_s"), (o.cs, "colsum"), (o.csx, "colsum_gx")):
+            t.check(f"{tag} {name}")      # (every reported partial row written: no sentinel left)
+        o.dwa.check(tag + " dw / dw2", dw_owned)
+        fold = o.csx.t.view(rows, 256).double().sum(0)
+        check(kind, fold, gx_ref.sum(0), gx_mag.sum(0), 64 + M + 2, tag + " colsum_gx", rounded=False)
+        check(kind, o.out.t, r.out, r.out_mag, 256, tag + " out")
+        check(kind, o.out_s.t, r2.out, r2.out_mag, 256, tag + " out_s")
+        b1_check_sums(kind, o.cs, rows, 64, o.dwa, 320, r, M, 256, tag)
+        check(kind, o.dwa.t.view(256, 320)[:, 64:128], r2.dw, r2.dw_mag, M, tag + " dw2", rounded=False)
+        assert bool((o.cs.t.view(rows // 8, 8, 64)[:, 4:] == 0).all()), \
+            f"{tag}: column-sum rows of waves 4-7 (the shortcut half) not zero"
+    assert torch.equal(a.out.t.view(torch.int16), b.out.t.view(torch.int16)), f"{what}: out differs without gx"
+    assert torch.equal(a.out_s.t.view(torch.int16), b.out_s.t.view(torch.int16)), f"{what}: out_s differs without gx"
+
