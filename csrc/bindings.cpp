@@ -498,7 +498,7 @@ void wgrad_f32(Tensor x, int64_t R, int64_t S, int64_t stride, int64_t pad, Tens
 }
 
 void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_t oy, int64_t ox, Tensor out,
-              OptT crop_dev, OptT mix) {
+              OptT crop_dev, OptT mix, OptT rrc) {
   pddl::StemParams p{};
   PCHECK(in.is_cuda() && in.is_contiguous() && in.dim() == 4 && in.size(3) == 3, "stem input must be [B,H,W,3]");
   PCHECK(in.scalar_type() == torch::kUInt8 || in.scalar_type() == torch::kFloat32, "stem input uint8 or fp32");
@@ -517,6 +517,12 @@ void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_
     p.flip = flip->data_ptr<uint8_t>();
   }
   p.mix = mix_table(mix, p.B);
+  if (rrc.has_value()) {   // a per-image box table (kernels.h): mode 3, whatever mode was passed
+    PCHECK(rrc->is_cuda() && rrc->scalar_type() == torch::kInt32 && rrc->is_contiguous() && rrc->dim() == 2 &&
+           rrc->size(1) == 4 && rrc->size(0) >= p.B, "rrc: contiguous device int32 [>= B][4]");
+    p.rrc = rrc->data_ptr<int32_t>();
+    p.mode = 3;
+  }
   p.scale = 1.f / 255.f;
   p.Hs = (int)((Hc + 6) / 2); p.Ws = (int)((Wc + 6) / 2);
   PCHECK(out.is_contiguous() && out.numel() >= (int64_t)p.B * p.Hs * p.Ws * 16, "stem s2d output too small");
@@ -966,7 +972,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prep_f32", &prep_f32, REL);
   m.def("wgrad_f32", &wgrad_f32, REL);
   m.def("stem_s2d", &stem_s2d, REL, py::arg("images"), py::arg("flip"), py::arg("mode"), py::arg("Hc"), py::arg("Wc"),
-        py::arg("oy"), py::arg("ox"), py::arg("out"), py::arg("crop_dev"), py::arg("mix") = py::none());
+        py::arg("oy"), py::arg("ox"), py::arg("out"), py::arg("crop_dev"), py::arg("mix") = py::none(),
+        py::arg("rrc") = py::none());
+  // (kernel tests) what the last stem_s2d launch ran: ("pixel" | "rows" | "band", s2d rows per band workgroup)
+  m.def("stem_last_launch", []() {
+    static const char* const form[] = {"pixel", "rows", "band"};
+    int f = 0, band = 0;
+    pddl::stem_last_launch(&f, &band);
+    return py::make_tuple(form[f], band);
+  });
   m.def("stem_wgrad_fold", &stem_wgrad_fold, REL);
   m.def("maxpool_fwd", &maxpool_fwd, REL);
   m.def("stem_pool_bwd", &stem_pool_bwd, REL, py::arg("x2"), py::arg("gpool"), py::arg("idx"), py::arg("dw"),
@@ -1019,6 +1033,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     else if (which == "igemm_pk") { TORCH_CHECK(v == 0 || (v >= 2 && v <= 4), "igemm_pk: 0 or ring depth 2-4"); pddl::g_igemm_pk = v; }
     else if (which == "wgrad8_min_rows") { TORCH_CHECK(v >= 64, "wgrad8_min_rows"); pddl::g_wgrad8_min_rows = v; }
     else if (which == "stem") pddl::g_stem_variant = v;
+    else if (which == "stem_rrc_band") { TORCH_CHECK(v >= 0, "stem_rrc_band: 0 (auto) or a band-height cap"); pddl::g_stem_rrc_band = v; }
     else if (which == "conv_f32") pddl::g_conv_f32_variant = v;
     else if (which == "conv_f32_splitk") pddl::g_conv_f32_splitk = v;
     else if (which == "conv_f32_sk_elig") { TORCH_CHECK(v >= 1 && v <= 8, "conv_f32_sk_elig: 1-8"); pddl::g_conv_f32_sk_elig = v; }

@@ -12,6 +12,7 @@
 // Every kernel moves 16 bytes per lane (8 x bf16) where the layout allows (Guideline 13).
 #include "common.h"
 #include "kernels.h"
+#include "stem_common.h"
 
 namespace pddl {
 
@@ -42,26 +43,7 @@ __device__ __forceinline__ float stem_pix(const StemParams& p, int b, int y, int
   return v * p.scale;
 }
 
-// Mixup / CutMix (MIX forms; p.mix is the per-image table [B][8] of kernels.h): image b's pixel
-// becomes w*A_b + (1 - w)*A_partner with w = 0 inside the row's box and w = w_pix outside, both
-// A's being stem_pix values (each image's own flip, the batch's crop).  The partner is clamped to
-// [0, B) and the box to the image, so a bad table gives a wrong picture, never a stray read.
-struct StemMix { int pb, y0, x0, y1, x1; float w; };
-__device__ __forceinline__ StemMix stem_mix_row(const StemParams& p, int b) {
-  const int32_t* r = p.mix + (long)b * 8;
-  StemMix m;
-  m.pb = min(max(r[0], 0), p.B - 1);
-  m.y0 = min(max(r[1], 0), p.Hc); m.x0 = min(max(r[2], 0), p.Wc);
-  m.y1 = min(max(r[3], 0), p.Hc); m.x1 = min(max(r[4], 0), p.Wc);
-  m.w = __int_as_float(r[5]);
-  return m;
-}
-__device__ __forceinline__ float stem_mix_weight(const StemMix& m, int y, int x) {
-  return (y >= m.y0 && y < m.y1 && x >= m.x0 && x < m.x1) ? 0.f : m.w;
-}
-// One explicit fma in every stem kernel (the row form stays bitwise equal to the per-pixel form);
-// w = 1 returns a and w = 0 returns b bit for bit.
-__device__ __forceinline__ float stem_mix_blend(float w, float a, float b) { return __fmaf_rn(w, a, (1.f - w) * b); }
+// (StemMix, stem_mix_row / _weight / _blend: stem_common.h, shared with stem_rrc.hip)
 template <bool MIX>
 __device__ __forceinline__ float stem_val(const StemParams& p, const StemMix& m, float w, int b, int y, int x, int c) {
   if (!MIX) return stem_pix(p, b, y, x, c);
@@ -123,6 +105,8 @@ const char* stem_s2d_f32_launch(const StemParams& p, float* out, hipStream_t s) 
   if ((p.Hc + 6) != 2 * p.Hs || (p.Wc + 6) != 2 * p.Ws) return "stem_s2d_f32: Hs must be (Hc + 6) / 2 (even crop)";
   const long npix = (long)p.B * p.Hs * p.Ws;
   if (npix >= (1L << 31) - (1L << 24)) return "stem_s2d_f32: too many pixels for 32-bit indexing";
+  if (p.mode == 3) return stem_rrc_launch(p, out, 1, s);   // random-resized-crop: stem_rrc.hip
+  stem_note_launch(0, 0);
   const int grid = (int)lmin((npix + 255) / 256, 16384);
   if (p.mix)
     hipLaunchKernelGGL(stem_s2d_f32_kernel<true>, dim3(grid), dim3(256), 0, s, p, out, (int)npix, fdiv_magic(p.Ws),
@@ -226,9 +210,12 @@ const char* stem_s2d_launch(const StemParams& p, hipStream_t s) {
   if ((p.Hc + 6) != 2 * p.Hs || (p.Wc + 6) != 2 * p.Ws) return "stem_s2d: Hs must be (Hc + 6) / 2 (even crop)";
   const long npix = (long)p.B * p.Hs * p.Ws;
   if (npix >= (1L << 31) - (1L << 24)) return "stem_s2d: too many pixels for 32-bit indexing";
+  if (p.mode == 3) return stem_rrc_launch(p, p.out, 0, s);   // random-resized-crop: stem_rrc.hip
+  stem_note_launch(0, 0);
   if (g_stem_variant == 1 && p.in_u8 && p.mode != 1 && p.Wc <= STEM_ROW_MAXW) {
     if (p.mix) hipLaunchKernelGGL(stem_s2d_rows_kernel<true>, dim3(p.B * p.Hs), dim3(128), 0, s, p);
     else hipLaunchKernelGGL(stem_s2d_rows_kernel<false>, dim3(p.B * p.Hs), dim3(128), 0, s, p);
+    stem_note_launch(1, 0);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }

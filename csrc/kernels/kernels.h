@@ -195,14 +195,25 @@ struct StemParams {
   const void* in; int in_u8;          // [B, Hin, Win, 3] uint8 or fp32 (0..255)
   int B, Hin, Win;
   int Hc, Wc;                         // preprocessed (cropped / resized) size
-  int mode;                           // 0 identity, 1 bilinear resize, 2 crop at (oy, ox)
+  int mode;                           // 0 identity, 1 bilinear resize, 2 crop at (oy, ox), 3 per-image box (rrc)
   int oy, ox;
   const int32_t* crop_dev;            // optional device {oy, ox} (overrides oy/ox; HIP-graph replays)
   const uint8_t* flip;                // per-image horizontal flip flags (nullable)
   float scale;                        // Rescaling(1/255)
   uint16_t* out; int Hs, Ws;          // space-to-depth image [B][Hs][Ws][16], Hs = (Hc + 6) / 2
   const int32_t* mix;                 // optional mixup / CutMix table [B][8] (below); null: no mixing
+  const int32_t* rrc;                 // mode 3: the random-resized-crop box table [B][4] (below)
 };
+// The per-image box table of mode 3, int32 [B][4], row b = {y0, x0, h, w}: a box of the Hin x Win
+// source in whole pixels that becomes image b's Hc x Wc picture (crop, then bilinear resize with
+// half-pixel centres, taps clamped to the box, no antialias).  The kernels clamp a row to
+// y0 = clamp(y0, 0, Hin - 1), h = clamp(h, 1, Hin - y0) (likewise in x): a bad table gives a wrong
+// picture, never a stray read.  Output row y reads box rows clamp(ty, 0, h-1), clamp(ty+1, 0, h-1)
+// with ty = floor(((2y+1)h - Hc) / 2Hc) and the weight fy = (((2y+1)h - Hc) - ty 2Hc) / 2Hc, all
+// in integers up to the one fp32 division (likewise in x, on the flipped output column); then, in
+// fp32 on the raw 0..255 values, horizontal first: top = fma(b - a, fx, a), bot = fma(d - c, fx, c),
+// v = fma(bot - top, fy, top) * scale.  {0, 0, Hc, Wc} is bitwise mode 0, {oy, ox, Hc, Wc} mode 2.
+// The mix table's box stays in the preprocessed image; the partner is resampled with its own row.
 // The per-image mix table, int32 [B][8], shared by the stem kernels and the training heads.  Row b:
 //   0      partner: index in this batch of the image mixed into image b
 //   1..4   y0, x0, y1, x1: half-open box in the Hc x Wc preprocessed image (after each image's own
@@ -216,6 +227,14 @@ struct StemParams {
 // conv then becomes a 4x4/s1 "window" implicit GEMM with K = 4*4*16 = 256.
 const char* stem_s2d_launch(const StemParams& p, hipStream_t s);
 const char* stem_s2d_f32_launch(const StemParams& p, float* out, hipStream_t s);   // fp32 image (out ignored)
+// Mode 3 (stem_rrc.hip; both launchers above forward to it): the band form for uint8 input whose
+// worst-case box fits the LDS budget, else the per-pixel form; out is bf16 or (out_f32) fp32.
+const char* stem_rrc_launch(const StemParams& p, void* out, int out_f32, hipStream_t s);
+// What the calling thread's last stem_s2d launch ran (tests): form 0 per-pixel, 1 row form, 2 band
+// form, and the band form's s2d rows per workgroup; kept per thread, since replicas launch from several.
+void stem_note_launch(int form, int band);
+void stem_last_launch(int* form, int* band);
+extern int g_stem_rrc_band;   // tuning knob like g_stem_variant: > 0 caps the band height
 // Fold the s2d-domain stem weight gradient [64][256] back to [64][7][7][3] (added into dw).
 const char* stem_wgrad_fold_launch(const float* g2, float* dw, int cout, hipStream_t s);
 

@@ -10,7 +10,7 @@ import argparse
 import dataclasses
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 
 @dataclass
@@ -55,6 +55,10 @@ class TrainConfig:
     mixup: float = 0.0                             # additive: mixup alpha (lambda ~ Beta(alpha, alpha)); 0 = off
     cutmix: float = 0.0                            # additive: CutMix alpha; 0 = off (both on: one of the two per batch)
     mix_prob: float = 1.0                          # probability that a training batch is mixed at all
+    rrc: bool = False                              # additive: random-resized-crop (a box per image, resized to
+                                                   # `crop` in the preprocess kernel) instead of RandomCrop
+    rrc_scale: Tuple[float, float] = (0.08, 1.0)   # the box's area as a fraction of the image, uniform
+    rrc_ratio: Tuple[float, float] = (3 / 4, 4 / 3)   # its aspect ratio w / h, log-uniform
     global_clipnorm: Optional[float] = None        # additive (Keras `global_clipnorm`): the whole gradient is scaled
                                                    # by C / max(|g|, C) before the update; None = off
     skip_nonfinite: bool = False                   # additive: a step whose gradient norm is inf / nan updates nothing
@@ -174,6 +178,17 @@ def check_mix(cfg: TrainConfig) -> None:
         raise ValueError(f"--mix-prob must be a number in [0, 1] (got {p!r})")
 
 
+def check_rrc(cfg: TrainConfig) -> None:
+    """--rrc-scale / --rrc-ratio LO HI: a bound that is no finite number > 0, LO > HI or a scale above 1
+    is a configuration error, raised before anything is built."""
+    for flag, r in (("--rrc-scale", cfg.rrc_scale), ("--rrc-ratio", cfg.rrc_ratio)):
+        ok = len(r) == 2 and all(not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v) and v > 0
+                                 for v in r)
+        if not ok or r[0] > r[1] or (flag == "--rrc-scale" and r[1] > 1):
+            raise ValueError(f"{flag} must be LO HI with 0 < LO <= HI{' <= 1' if flag == '--rrc-scale' else ''} "
+                             f"(got {tuple(r)!r})")
+
+
 def check_clip(cfg: TrainConfig) -> None:
     """--global-clipnorm C / --skip-nonfinite: a threshold that is no finite number > 0, or either
     option on the parameter server, is a configuration error, raised before anything is built."""
@@ -224,6 +239,14 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "of the two with probability 1/2")
     a("--mix-prob", type=float, dest="mix_prob", metavar="P",
       help="probability in [0, 1] that a training batch is mixed (default 1; needs --mixup or --cutmix)")
+    a("--rrc", action="store_true", default=None,
+      help="random-resized-crop (the Inception / torchvision augmentation): each training image is a random box of "
+           "its source, resized to --crop inside the preprocess kernel (bilinear, no antialias); replaces the "
+           "per-batch RandomCrop offset")
+    a("--rrc-scale", type=float, nargs=2, dest="rrc_scale", metavar=("LO", "HI"),
+      help="the box's area as a fraction of the image, uniform in [LO, HI] (default 0.08 1.0)")
+    a("--rrc-ratio", type=float, nargs=2, dest="rrc_ratio", metavar=("LO", "HI"),
+      help="the box's aspect ratio w / h, log-uniform in [LO, HI] (default 0.75 1.3333)")
     a("--global-clipnorm", type=float, dest="global_clipnorm",
       help="C > 0: scale the whole gradient by C / max(|g|, C) before the update (Keras global_clipnorm), the norm "
            "taken on the device in a fixed order; with --accum-steps K the optimizer only runs on the K-th "

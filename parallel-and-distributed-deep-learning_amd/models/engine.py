@@ -55,6 +55,11 @@ def _mix_kw(mix):
     return {} if mix is None else {"mix": mix}
 
 
+def _rrc_kw(rrc):
+    """The `rrc=` keyword of the stem launch: absent without a random-resized-crop box table."""
+    return {} if rrc is None else {"rrc": rrc}
+
+
 class HipEngine(SideStream):
     BN_MODES = ("frozen",)   # HipEngineBNTrain (models/engine_bn.py) runs bn_mode="train"
     FUSE_PROJ_OK = True     # projection blocks: conv3 + shortcut conv as one dual-source GEMM
@@ -578,7 +583,7 @@ class HipEngine(SideStream):
             return 1, 0, 0
         return 2, crop_offset[0], crop_offset[1]
 
-    def _forward(self, images, B, training, flip, crop_offset, mix=None):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None, rrc=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         mode, oy, ox = self._stem_mode(training, crop_offset)
@@ -587,7 +592,7 @@ class HipEngine(SideStream):
         if mode == 2 and isinstance(crop_offset, torch.Tensor):   # device offsets (graph capture)
             crop_dev, oy, ox = crop_offset, 0, 0
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
-                   **_mix_kw(mix if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
         H1, H2, Hs = self.H1, self.H2, self.Hs
         s = L.stem
         pool = self.pool[:B]
@@ -696,7 +701,7 @@ class HipEngine(SideStream):
 
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -706,7 +711,7 @@ class HipEngine(SideStream):
         self.ws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset, mix)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix, rrc)
         prof.pop()
         prof.push("step/backward")
         logits = self.logits[:B]

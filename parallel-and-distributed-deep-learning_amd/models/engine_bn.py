@@ -26,7 +26,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
-from .engine import IGEMM_DGRAD, STEM_K, HipEngine, _mix_kw
+from .engine import IGEMM_DGRAD, STEM_K, HipEngine, _mix_kw, _rrc_kw
 from ..utils import profiling as prof
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout
 
@@ -189,7 +189,7 @@ class HipEngineBNTrain(HipEngine):
             N.bn_stats(self.acc, st, nst, maxc, True, self.params, self.bn_mean, self.bn_inv, self.bn_scale,
                        self.bn_shift, BN_EPS, BN_MOMENTUM)
 
-    def _forward(self, images, B, training, flip, crop_offset, mix=None):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None, rrc=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         tabs = self._launch_tables(B) if training else None
@@ -202,7 +202,7 @@ class HipEngineBNTrain(HipEngine):
         if mode == 2 and isinstance(crop_offset, torch.Tensor):
             crop_dev, oy, ox = crop_offset, 0, 0
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
-                   **_mix_kw(mix if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
         H1, Hs = self.H1, self.Hs
         s = L.stem
         zs = self.zs[:B]
@@ -292,7 +292,7 @@ class HipEngineBNTrain(HipEngine):
                             sg=self.bsg, sgx=self.bsgx, dz=out, grads=self.grads, coef=self.bcoef)
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -300,7 +300,7 @@ class HipEngineBNTrain(HipEngine):
         self.bws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset, mix)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix, rrc)
         prof.pop()
         prof.push("step/backward")
         logits = self.logits[:B]

@@ -29,7 +29,7 @@ import torch
 from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
-from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw
+from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw, _rrc_kw
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 from .side_stream import SideStream
 
@@ -266,13 +266,13 @@ class HipF32Engine(SideStream):
         self._conv(x, c.k, c.stride, c.pad, out.shape[1], self._w(c.name, c.cout, c.k * c.k * c.cin), out,
                    self.scale[ch:], self.shift[ch:], res, relu)
 
-    def _forward(self, images, B, training, flip, crop_offset, mix=None):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None, rrc=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
-                   **_mix_kw(mix if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
         s = L.stem
         c1 = self.c1[:B]
         ch = self.ch[s.name]
@@ -307,14 +307,14 @@ class HipF32Engine(SideStream):
 
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
         self.ws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset, mix)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix, rrc)
         prof.pop()
         prof.push("step/backward")
         ncls = self.num_classes
@@ -564,7 +564,7 @@ class HipF32EngineBNTrain(HipF32Engine):
             self.N.bn_stats(self.acc, self._stats(c, M), 1, c.cout, True, self.params, self.bn_mean, self.bn_inv,
                             self.bn_scale, self.bn_shift, BN_EPS, BN_MOMENTUM)
 
-    def _forward(self, images, B, training, flip, crop_offset, mix=None):
+    def _forward(self, images, B, training, flip, crop_offset, mix=None, rrc=None):
         self.N.splitk_use(self.splitk_ws)   # this engine's split-K workspace, for this thread's launches
         N, L = self.N, self.L
         if not training:   # the moving statistics for every layer at once
@@ -573,7 +573,7 @@ class HipF32EngineBNTrain(HipF32Engine):
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
-                   **_mix_kw(mix if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
         s = L.stem
         zs, c1 = self.zs[:B], self.c1[:B]
         self._z(s, x2, 4, 1, 0, self.H1, self.wf32[:64 * STEM_K].view(64, STEM_K), zs, training)
@@ -632,7 +632,7 @@ class HipF32EngineBNTrain(HipF32Engine):
                            self.bn_inv, self.bsg, self.bsgx, out, out2, self.grads, self.bcoef)
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
-                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None):
+                         bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
         N, L = self.N, self.L
         B = images.shape[0]
         assert B <= self.cap, "batch larger than the engine's buffers"
@@ -640,7 +640,7 @@ class HipF32EngineBNTrain(HipF32Engine):
         self.bws.zero_()
         lab = self._labels(labels, B)
         prof.push("step/forward")
-        x5 = self._forward(images, B, True, flip, crop_offset, mix)
+        x5 = self._forward(images, B, True, flip, crop_offset, mix, rrc)
         prof.pop()
         prof.push("step/backward")
         ncls = self.num_classes

@@ -53,10 +53,53 @@ def mix_targets(labels: torch.Tensor, mix: torch.Tensor, num_classes: int, label
     return w * T + (1.0 - w) * T[partner], torch.where(w_lab >= 0.5, labels, labels[partner])
 
 
+def rrc_taps(o: torch.Tensor, n: torch.Tensor, N: int):
+    """Output indices o [B][N] along box sides of n [B] source pixels: the two box-relative taps and
+    the fp32 weight of the second, in integers up to one division (kernels.h, `StemParams::rrc`)."""
+    n = n.view(-1, 1)
+    num = (2 * o + 1) * n - N
+    t = torch.div(num, 2 * N, rounding_mode="floor")
+    f = (num - t * 2 * N).float() / float(2 * N)
+    hi = n - 1
+    return torch.minimum(t.clamp_min(0), hi), torch.minimum((t + 1).clamp_min(0), hi), f
+
+
+def rrc_resample(images: torch.Tensor, rrc: torch.Tensor, Hc: int, Wc: int, flip: Optional[torch.Tensor] = None):
+    """[B,H,W,3] (0..255) -> NCHW float32 in [0,1] at Hc x Wc: image b's box rrc[b] = (y0, x0, h, w),
+    clamped to the image as the kernels clamp it, resized with bilinear taps clamped to the box
+    (half-pixel centres, no antialias), horizontal lerp first, in fp32 on the raw values; the flip
+    acts on the output column."""
+    B, H, W, _ = images.shape
+    dev = images.device
+    t = rrc[:B].to(dev).long()
+    y0, x0 = t[:, 0].clamp(0, H - 1), t[:, 1].clamp(0, W - 1)
+    h, w = torch.minimum(t[:, 2].clamp_min(1), H - y0), torch.minimum(t[:, 3].clamp_min(1), W - x0)
+    ys = torch.arange(Hc, device=dev).expand(B, Hc)
+    xs = torch.arange(Wc, device=dev).expand(B, Wc)
+    if flip is not None:
+        xs = torch.where(flip.to(dev).bool().view(B, 1), Wc - 1 - xs, xs)
+    ya, yb, fy = rrc_taps(ys, h, Hc)
+    xa, xb, fx = rrc_taps(xs, w, Wc)
+    img = images.float()
+    bi = torch.arange(B, device=dev).view(B, 1, 1)
+
+    def tap(yy, xx):
+        return img[bi, (y0.view(B, 1) + yy).view(B, Hc, 1), (x0.view(B, 1) + xx).view(B, 1, Wc)]   # [B,Hc,Wc,3]
+    fx, fy = fx.view(B, 1, Wc, 1), fy.view(B, Hc, 1, 1)
+    top = tap(ya, xa) + (tap(ya, xb) - tap(ya, xa)) * fx
+    bot = tap(yb, xa) + (tap(yb, xb) - tap(yb, xa)) * fx
+    return ((top + (bot - top) * fy) * (1.0 / 255.0)).permute(0, 3, 1, 2)
+
+
 def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[torch.Tensor] = None,
-               crop_offset=(0, 0), mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+               crop_offset=(0, 0), mix: Optional[torch.Tensor] = None,
+               rrc: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[B,H,W,3] uint8/float (0..255) -> NCHW float32 in [0,1] at crop x crop.  mix (training
-    only): a mixup / CutMix table, applied after each image's own crop and flip."""
+    only): a mixup / CutMix table, applied after each image's own crop and flip.  rrc (training
+    only): a random-resized-crop box table, which replaces the crop / resize."""
+    if training and rrc is not None:
+        x = rrc_resample(images, rrc, crop, crop, flip)
+        return mix_pixels(x, mix) if mix is not None else x
     x = images.float().permute(0, 3, 1, 2) * (1.0 / 255.0)
     H, W = x.shape[-2:]
     if crop > H or crop > W or (not training and crop != H):
@@ -257,14 +300,14 @@ class TorchEngine:
         pass
 
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0), bucket_cb=None, buckets=None,
-                         mix=None):
+                         mix=None, rrc=None):
         # leaf over the trainable prefix; BN statistics are read (and, in train mode,
         # updated in place) straight from the flat buffer
         # (a copy: BN statistics share the flat buffer and train-mode BN updates them in place)
         p = self.params[: self.L.n_trainable].clone().requires_grad_(True)
         self.model.stats = self.params
         self.model.bind(p)
-        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix)
+        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix, rrc)
         logits = self.model.logits(p, x, training=True)
         lab = counted = labels.to(self.device)
         if mix is not None:

@@ -826,7 +826,8 @@ def run_ps_job(cfg, num_ps: Optional[int] = None, num_workers: Optional[int] = N
     """Entry of imagenet-resnet50-ps.py.  Under torchrun (WORLD_SIZE = P + W) every process
     takes its role from RANK; otherwise spawn the whole cluster locally (the reference's
     create_in_process_cluster, imagenet-resnet50-ps.py:31-65)."""
-    from ..config import check_accum, check_clip, check_loss, check_mix
+    from ..config import check_accum, check_clip, check_loss, check_mix, check_rrc
+    check_rrc(cfg)
     check_mix(cfg)                                # (--mixup / --cutmix: every worker mixes its own batches)
     check_accum(cfg)                              # (--accum-steps > 1: every push is one asynchronous update)
     check_clip(cfg)                               # (no process here holds a whole gradient to take the norm of)
@@ -923,7 +924,8 @@ class ParameterServerStrategy:
         if cl.device.type == "cuda" and hasattr(eng, "wbf") and cfg.graphs is True:
             from ..train.graph import GraphedTrainStep   # forward + backward as one HIP graph
             self.graphed = GraphedTrainStep(eng, None, cfg.batch_size, (cfg.image_size, cfg.image_size),
-                                            1.0 / cfg.batch_size, with_optimizer=False, mix=self.aug.mixing)
+                                            1.0 / cfg.batch_size, with_optimizer=False, mix=self.aug.mixing,
+                                            rrc=self.aug.boxes.enabled)
         self.acc = torch.zeros(2, dtype=torch.float64, device=cl.device)
         self.n_img = 0
 
@@ -936,9 +938,10 @@ class ParameterServerStrategy:
         flip, off = self.aug(B)
         g = self.graphed
         if g is not None and B == g.B and tuple(images.shape[1:3]) == tuple(g.images.shape[1:3]):
-            s = g(images, labels, flip, off, self.aug.mix(B, graphed=True))
+            s = g(images, labels, flip, off, self.aug.mix(B, graphed=True), self.aug.rrc(B))
         else:
-            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=self.aug.mix(B))
+            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=self.aug.mix(B),
+                                     rrc=self.aug.rrc(B))
         self.acc.add_(s[:2])            # (device-side: no per-step device -> host read)
         self.n_img += B
         if self.cfg.ps_overlap:

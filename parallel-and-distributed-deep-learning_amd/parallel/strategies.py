@@ -26,8 +26,9 @@ import torch.distributed as dist
 
 from ..data.datasets import Pipeline, make_source
 from ..models.resnet50 import ParamLayout
-from ..train.mix import COLS, MixSampler, identity_table
+from ..train.mix import MixSampler, identity_table
 from ..train.optim import make_optimizer
+from ..train.rrc import RrcSampler
 from ..utils import profiling as prof
 from ..utils.envopts import opt
 from .collectives import BucketAllReducer
@@ -102,7 +103,8 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
 
 class Augment:
     """RandomFlip (per image) and RandomCrop offset (per batch, crop < input) draws, and the
-    mixup / CutMix table of --mixup / --cutmix (`mix`; train/mix.py)."""
+    mixup / CutMix table of --mixup / --cutmix (`mix`; train/mix.py) and the random-resized-crop
+    box table of --rrc (`rrc`; train/rrc.py), which replaces the RandomCrop offset."""
 
     MIX_STAGES = 4     # pinned staging buffers of the table upload, used in turn
 
@@ -114,8 +116,10 @@ class Augment:
         # (a generator of its own: the flip / crop draws above are the same with mixing on or off)
         self.sampler = MixSampler(getattr(cfg, "mixup", 0.0), getattr(cfg, "cutmix", 0.0),
                                   getattr(cfg, "mix_prob", 1.0), cfg.crop, cfg.crop, seed)
-        self._stage = []       # [(pinned host table, event of its last upload)]
-        self._turn = 0
+        self.boxes = RrcSampler(getattr(cfg, "rrc", False), getattr(cfg, "rrc_scale", (0.08, 1.0)),
+                                getattr(cfg, "rrc_ratio", (3 / 4, 4 / 3)), cfg.image_size, cfg.image_size, seed)
+        self._stages = {}      # table kind -> [[pinned host table, event of its last upload]], used in turn
+        self._turns = {}
 
     @property
     def mixing(self) -> bool:
@@ -135,17 +139,28 @@ class Augment:
             if not graphed:
                 return None
             t = identity_table(B)
+        return self._upload("mix", t)
+
+    def rrc(self, B):
+        """The device table [B][4] of this batch's random-resized-crop boxes (one draw per image),
+        uploaded like the mix table; None without --rrc."""
+        if not self.boxes.enabled:
+            return None
+        return self._upload("rrc", self.boxes.draw(B))
+
+    def _upload(self, kind, t):
+        B, cols = t.shape
         dev = torch.device(self.device)
         if dev.type != "cuda":
             return torch.from_numpy(t)
-        if not self._stage:
-            self._stage = [[None, None] for _ in range(self.MIX_STAGES)]
-        slot = self._stage[self._turn % self.MIX_STAGES]
-        self._turn += 1
+        stage = self._stages.setdefault(kind, [[None, None] for _ in range(self.MIX_STAGES)])
+        turn = self._turns.get(kind, 0)
+        self._turns[kind] = turn + 1
+        slot = stage[turn % self.MIX_STAGES]
         if slot[0] is None or slot[0].shape[0] < B or not slot[1].query():
             # (first use, a larger batch, or -- the host more than MIX_STAGES steps ahead -- an upload
             # still in flight: a fresh buffer, never a wait; the copy keeps the old one alive)
-            slot[0] = torch.empty(B, COLS, dtype=torch.int32).pin_memory()
+            slot[0] = torch.empty(B, cols, dtype=torch.int32).pin_memory()
         host = slot[0][:B]
         host.copy_(torch.from_numpy(t))
         out = host.to(dev, non_blocking=True)
@@ -158,7 +173,7 @@ class Augment:
         if self.cfg.flip:
             flip = torch.randint(0, 2, (B,), dtype=torch.uint8, device=self.device, generator=self.gen)
         off = (0, 0)
-        if self.cfg.crop < self.cfg.image_size:
+        if self.cfg.crop < self.cfg.image_size and not self.boxes.enabled:   # (--rrc: each image has its own box)
             m = self.cfg.image_size - self.cfg.crop
             off = (int(self.rng.integers(0, m + 1)), int(self.rng.integers(0, m + 1)))
         return flip, off
@@ -168,10 +183,11 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
-        from ..config import check_accum, check_clip, check_loss, check_mix
+        from ..config import check_accum, check_clip, check_loss, check_mix, check_rrc
         check_accum(cfg)
         check_loss(cfg)
         check_mix(cfg)
+        check_rrc(cfg)
         check_clip(cfg)
         self.cfg = cfg
         self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
@@ -330,7 +346,7 @@ class SingleStrategy(Strategy):
             from ..train.graph import GraphedTrainStep   # HIP-graph replay of the whole step
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B, mix=self.aug.mixing)
+                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.boxes.enabled)
 
     def train_step(self, images, labels):
         self._fault_tick()
@@ -338,14 +354,15 @@ class SingleStrategy(Strategy):
         flip, off = self.aug(B)
         if self.graphed is not None and B == self.graphed.B and tuple(images.shape[1:3]) == self.graphed.images.shape[1:3]:
             return self.graphed(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
-                                flip, off, self.aug.mix(B, graphed=True)).clone()
+                                flip, off, self.aug.mix(B, graphed=True), self.aug.rrc(B)).clone()
         eng = self.engine
         acc = self.accum
         mix = self.aug.mix(B)
+        rrc = self.aug.rrc(B)
         if acc is None:
-            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=mix).clone()
+            s = eng.forward_backward(images, labels, 1.0 / B, flip=flip, crop_offset=off, mix=mix, rrc=rrc).clone()
         else:            # a micro-step: the update runs on every K-th call, from the mean over K batches
-            s = eng.forward_backward(images, labels, 1.0 / (B * acc.k), flip=flip, crop_offset=off, mix=mix).clone()
+            s = eng.forward_backward(images, labels, 1.0 / (B * acc.k), flip=flip, crop_offset=off, mix=mix, rrc=rrc).clone()
             acc.accumulate()
             if not acc.advance():
                 return s
@@ -413,7 +430,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
             from ..train.graph import GraphedTrainStep   # one rank: the whole step as one HIP graph
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B, mix=self.aug.mixing)
+                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.boxes.enabled)
         # bucket_mb <= 0: autotune (Horovod's HOROVOD_AUTOTUNE analogue for the fusion threshold)
         self._tune = None
         mb = self.cfg.bucket_mb
@@ -499,7 +516,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
         if g is not None and images.shape[0] == g.B and tuple(images.shape[1:3]) == tuple(g.images.shape[1:3]):
             flip, off = self.aug(images.shape[0])
             return g(images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True),
-                     flip, off, self.aug.mix(images.shape[0], graphed=True)).clone()
+                     flip, off, self.aug.mix(images.shape[0], graphed=True), self.aug.rrc(images.shape[0])).clone()
         s = self.compute_gradients(images, labels)
         if not self._update_due:       # (--accum-steps: micro-steps 1..K-1 only accumulate)
             return s
@@ -537,7 +554,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
         if acc is not None and cb is not None:
             cb = acc.wrap(cb)
         s = self.engine.forward_backward(images, labels, gscale, flip=flip, crop_offset=off, bucket_cb=cb,
-                                         buckets=bks, mix=self.aug.mix(B)).clone()
+                                         buckets=bks, mix=self.aug.mix(B), rrc=self.aug.rrc(B)).clone()
         if acc is not None:
             if cb is None:
                 acc.accumulate()
@@ -832,7 +849,8 @@ class _LocalReplicas:
         for (eng, optim), d in zip(self.replicas, self.devices):
             with torch.cuda.device(d):
                 g = SegmentedStepGraphs(eng, optim, B, (H, W), 1.0 / global_batch, self.buckets,
-                                        image_dtype=parts[0][0].dtype, mix=self.augs[len(self.graphs)].mixing)
+                                        image_dtype=parts[0][0].dtype, mix=self.augs[len(self.graphs)].mixing,
+                                        rrc=self.augs[len(self.graphs)].boxes.enabled)
                 g.capture()
                 self.graphs.append(g)
         self.comm_streams = [torch.cuda.Stream(device=d) for d in self.devices]
@@ -902,7 +920,7 @@ class _LocalReplicas:
         for r, (g, d) in enumerate(zip(self.graphs, self.devices)):
             with torch.cuda.device(d):
                 flip, off = self.augs[r](B)
-                g.load(parts[r][0], parts[r][1], flip, off, self.augs[r].mix(B, graphed=True))
+                g.load(parts[r][0], parts[r][1], flip, off, self.augs[r].mix(B, graphed=True), self.augs[r].rrc(B))
         P = self._plan(cur, amb)
         streams = P["comm"]
         tl = self.tl
@@ -1074,7 +1092,7 @@ class _LocalReplicas:
                 cb = self._bucket_cb(i)
                 kw = dict(bucket_cb=accs[i].wrap(cb) if accs is not None else cb, buckets=self.buckets)
             stats[i] = eng.forward_backward(im, lb, gscale, flip=flip, crop_offset=off,
-                                            mix=self.augs[i].mix(im.shape[0]), **kw).clone()
+                                            mix=self.augs[i].mix(im.shape[0]), rrc=self.augs[i].rrc(im.shape[0]), **kw).clone()
             if accs is not None:
                 if not overlap:
                     accs[i].accumulate()
@@ -1150,7 +1168,7 @@ class _LocalReplicas:
             flip, off = self.augs[0](im.shape[0])
             accs = self._accums()
             s = eng.forward_backward(im, lb, 1.0 / (global_batch * self.accum_k), flip=flip, crop_offset=off,
-                                     mix=self.augs[0].mix(im.shape[0])).clone()
+                                     mix=self.augs[0].mix(im.shape[0]), rrc=self.augs[0].rrc(im.shape[0])).clone()
             if accs is not None:
                 accs[0].accumulate()
                 if not accs[0].advance():
@@ -1167,10 +1185,10 @@ class _LocalReplicas:
         g = getattr(self, "_whole", None)
         if g is None or g.B != B or g.gscale != 1.0 / global_batch or tuple(g.images.shape[1:3]) != tuple(im.shape[1:3]):
             g = self._whole = GraphedTrainStep(eng, opt, B, tuple(im.shape[1:3]), 1.0 / global_batch,
-                                               image_dtype=im.dtype, mix=self.augs[0].mixing)
+                                               image_dtype=im.dtype, mix=self.augs[0].mixing, rrc=self.augs[0].boxes.enabled)
         with torch.cuda.device(d):
             flip, off = self.augs[0](B)
-            return g(im, lb, flip, off, self.augs[0].mix(B, graphed=True)).clone()
+            return g(im, lb, flip, off, self.augs[0].mix(B, graphed=True), self.augs[0].rrc(B)).clone()
 
 
 class MirroredStrategy(Strategy):

@@ -234,6 +234,9 @@ class JsonlLogger(Callback):
         rec["mixup"] = float(getattr(self.trainer.cfg, "mixup", 0.0))
         rec["cutmix"] = float(getattr(self.trainer.cfg, "cutmix", 0.0))
         rec["mix_prob"] = float(getattr(self.trainer.cfg, "mix_prob", 1.0))
+        rec["rrc"] = bool(getattr(self.trainer.cfg, "rrc", False))
+        rec["rrc_scale"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_scale", (0.08, 1.0))]
+        rec["rrc_ratio"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_ratio", (3 / 4, 4 / 3))]
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)

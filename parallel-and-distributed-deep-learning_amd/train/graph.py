@@ -7,9 +7,10 @@ replayed with a single launch, which removes host launch cost and inter-kernel g
 what keeps small per-GPU batches, e.g. the reference's 32, from being launch-bound).
 
 Everything that changes between steps lives in device memory the graph reads:
-  * inputs are copied into static buffers (images, labels, flip flags, crop offset and, for a job
-    with --mixup / --cutmix, the per-image mix table: a batch that is not mixed loads the identity
-    table, which is bitwise the unmixed step, so one graph serves both),
+  * inputs are copied into static buffers (images, labels, flip flags, crop offset, for a job
+    with --rrc the per-image box table and, for a job with --mixup / --cutmix, the per-image mix
+    table: a batch that is not mixed loads the identity table, which is bitwise the unmixed
+    step, so one graph serves both),
   * the optimizer's step counter and learning rate are the device buffer `opt.hs`
     (train/optim.py), advanced by a kernel inside the graph; host LR changes are written to
     it between replays.
@@ -25,6 +26,7 @@ from typing import Optional, Tuple
 import torch
 
 from .mix import identity_table
+from .rrc import full_table
 
 
 # Capture in thread-local mode: under the default global mode any potentially unsafe HIP call
@@ -74,7 +76,7 @@ class GraphedTrainStep:
     parameter-server worker, whose update runs on the PS)."""
 
     def __init__(self, engine, optimizer, batch: int, image_hw: Tuple[int, int], gscale: float,
-                 image_dtype=torch.uint8, with_optimizer: bool = True, mix: bool = False):
+                 image_dtype=torch.uint8, with_optimizer: bool = True, mix: bool = False, rrc: bool = False):
         if not engine.params.is_cuda:
             raise RuntimeError("GraphedTrainStep needs the GPU engine")
         self.engine, self.opt, self.B, self.gscale = engine, optimizer, batch, float(gscale)
@@ -92,6 +94,9 @@ class GraphedTrainStep:
         # mix=True (a job with mixup / CutMix): the step is captured with the static mix table
         self.mix = torch.from_numpy(identity_table(batch)).to(dev) if mix else None
         self._mix_identity = True     # (mix holds the identity table: a table-less load needs no copy)
+        # rrc=True (a job with --rrc): the step is captured with the static box table (whole-image boxes
+        # until the first load; every load of such a step brings its batch's table)
+        self.rrc = torch.from_numpy(full_table(batch, *image_hw)).to(dev) if rrc else None
         self._flip_zero = True        # (flip holds zeros: a flip-less load needs no memset)
         self._crop_host = (0, 0)      # (the tuple crop currently in `crop`: unchanged -> no copy)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -107,9 +112,17 @@ class GraphedTrainStep:
         return stats
 
     def _mix_kw(self):
-        return {} if self.mix is None else {"mix": self.mix}
+        kw = {} if self.mix is None else {"mix": self.mix}
+        if self.rrc is not None:
+            kw["rrc"] = self.rrc
+        return kw
 
-    def _load(self, images, labels, flip, crop_offset, mix=None):
+    def _load(self, images, labels, flip, crop_offset, mix=None, rrc=None):
+        if (rrc is None) != (self.rrc is None):
+            raise ValueError("a step built with GraphedTrainStep(rrc=True) takes a box table at every load, "
+                             "one built without takes none")
+        if rrc is not None:
+            self.rrc.copy_(rrc[:self.B], non_blocking=True)
         if mix is None:
             if not self._mix_identity:
                 self.mix.copy_(torch.from_numpy(identity_table(self.B)), non_blocking=True)
@@ -155,8 +168,8 @@ class GraphedTrainStep:
             self.opt._iterations = it    # the capture pass did not step (no setter: hs is current)
         self.graph = g
 
-    def __call__(self, images, labels, flip=None, crop_offset=(0, 0), mix=None):
-        self._load(images, labels, flip, crop_offset, mix)
+    def __call__(self, images, labels, flip=None, crop_offset=(0, 0), mix=None, rrc=None):
+        self._load(images, labels, flip, crop_offset, mix, rrc)
         if self.graph is None:
             out = self._body()        # first call: eager (builds the engine's tables), then capture
             self.capture()
@@ -183,8 +196,8 @@ class SegmentedStepGraphs(GraphedTrainStep):
 
     def __init__(self, engine, optimizer, batch: int, image_hw: Tuple[int, int], gscale: float, buckets,
                  image_dtype=torch.uint8, two_stream: Optional[bool] = None, keep_graph: bool = False,
-                 probe=None, mix: bool = False):
-        super().__init__(engine, optimizer, batch, image_hw, gscale, image_dtype, with_optimizer=False, mix=mix)
+                 probe=None, mix: bool = False, rrc: bool = False):
+        super().__init__(engine, optimizer, batch, image_hw, gscale, image_dtype, with_optimizer=False, mix=mix, rrc=rrc)
         self.buckets = list(buckets)
         self.segments = []
         self.side_segments = []          # deferred engines: segment k's weight-gradient graph (or None)
@@ -313,8 +326,8 @@ class SegmentedStepGraphs(GraphedTrainStep):
         self.side_segments = sides if deferred else [None] * nb
         self.opt_graph = og
 
-    def load(self, images, labels, flip=None, crop_offset=(0, 0), mix=None):
-        self._load(images, labels, flip, crop_offset, mix)
+    def load(self, images, labels, flip=None, crop_offset=(0, 0), mix=None, rrc=None):
+        self._load(images, labels, flip, crop_offset, mix, rrc)
 
     def replay_segment(self, k: int):
         if self.segments[k] is not None:

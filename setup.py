@@ -31,6 +31,10 @@ HIP_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-ffp-contract=fast"
 # A/B builds of compile-time kernel parameters, e.g. PDDL_HIP_DEFINES="-DIGEMM_MIN_BLOCKS_1=4"
 # (use a separate PDDL_BUILD_TEMP: objects are rebuilt on source changes only)
 HIP_FLAGS += os.environ.get("PDDL_HIP_DEFINES", "").split()
+# Per-file flags.  stem_rrc.hip is compiled without the packed-fp32 VALU forms (v_pk_fma_f32,
+# v_pk_mul_f32, v_pk_add_f32).  The kernels are memory-bound: built with and without the flag they
+# pass the same tests and take the same time (profiles/rrc.txt), so the plainer code costs nothing.
+FILE_FLAGS = {"stem_rrc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def compile_kernels():
@@ -45,7 +49,7 @@ def compile_kernels():
         obj = os.path.join(odir, os.path.basename(src)[:-4] + ".o")
         if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_mtime):
             return obj
-        r = subprocess.run([HIPCC, *HIP_FLAGS, "-c", src, "-o", obj], capture_output=True, text=True)
+        r = subprocess.run([HIPCC, *HIP_FLAGS, *FILE_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stdout}\n{r.stderr}")
         return obj
