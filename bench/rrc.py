@@ -9,7 +9,13 @@ windows per case, their median, the windows printed).  Per batch and source size
 (the row form: identity, or RandomCrop at one offset), the band form of mode 3 on boxes drawn by
 train/rrc.py with the default ranges, and its per-pixel twin.  GB/s counts the bytes a launch must
 move: the boxes' pixels (the partner's too under a table) and the s2d image written; next to the
-6.29 TB/s measured HBM peak.  Then one batch-256 HipEngine step with and without a box table."""
+6.29 TB/s measured HBM peak.  Then one batch-256 HipEngine step with and without a box table.
+
+    python bench/rrc.py --antialias [--out profiles/rrc_antialias.txt]
+
+The rows of --antialias instead: 512 -> 224 and 384 -> 224 with boxes drawn from the whole source, the
+band and the per-pixel antialias forms and mode 3 (no antialias) on the same input, with and without
+a mixup table; then a batch-256 step at 448 -> 224 with and without the flag."""
 import argparse
 import json
 import os
@@ -64,22 +70,58 @@ def kernel_rows(batches, emit):
             torch.cuda.empty_cache()
 
 
-def step_rows(emit):
+def antialias_rows(batches, emit):
+    N = require_native()
+    N.allow_knob_changes(True)
+    dev = torch.device("cuda", 0)
+    hs = (CROP + 6) // 2
+    for B in batches:
+        mix = torch.from_numpy(mixup_table(np.random.default_rng(B).permutation(B), 0.7)).to(dev)
+        x2 = torch.empty(B, hs, hs, 16, dtype=torch.bfloat16, device=dev)
+        for S in (512, 384):
+            g = torch.Generator(device=dev).manual_seed(S)
+            img = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, device=dev, generator=g)
+            flip = torch.randint(0, 2, (B,), dtype=torch.uint8, device=dev, generator=g)
+            t = RrcSampler(True, (0.08, 1.0), (3 / 4, 4 / 3), S, S, 0).draw(B)
+            rrc = torch.from_numpy(t).to(dev)
+            area = int((t[:, 2].astype(np.int64) * t[:, 3]).sum())
+            for mixed in (False, True):
+                kw = {"mix": mix} if mixed else {}
+                nbytes = area * 3 * (2 if mixed else 1) + x2.numel() * 2     # every box pixel once, the image written
+                for name, variant, aa in (("antialias band", 1, True), ("antialias pixel", 0, True), ("mode 3 band", 1, False)):
+                    N.set_variant("stem", variant)
+                    fn = (lambda: N.stem_s2d(img, flip, 0, CROP, CROP, 0, 0, x2, None, **kw, rrc=rrc, antialias=aa))
+                    med, w = windows(fn, 20 if variant == 0 else 100 if B > 1000 else 400)
+                    form, band = N.stem_last_launch()
+                    N.set_variant("stem", 1)
+                    emit({"case": f"stem_s2d {S}->{CROP} {name} mix={'mixup' if mixed else 'none'}", "batch": B, "form": form,
+                          "band": band, "us": round(med, 2), "windows_us": [round(x, 2) for x in w],
+                          "GBps": round(nbytes / med / 1e3, 1), "of_peak": round(nbytes / (med * 1e-6) / HBM_PEAK, 3)})
+            del img
+            torch.cuda.empty_cache()
+
+
+def step_rows(emit, S=256, antialias=(False,)):
     """One batch-256 HipEngine training step (forward, backward, Adam, re-prep), eager, 256 -> 224:
     RandomCrop at one offset against a box table, alternated."""
     from pddl.models.engine import HipEngine
     from pddl.models.resnet50 import ParamLayout
     from pddl.train.optim import make_optimizer
-    B, S = 256, 256
+    B = 256
     dev = torch.device("cuda", 0)
-    eng = HipEngine(ParamLayout(), B, crop=CROP, image_size=S)
-    eng.init(seed=0)
-    opt = make_optimizer("adam", eng, lr=1e-3)
     img = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, device=dev)
     lab = torch.randint(0, 1000, (B,), device=dev)
     flip = torch.randint(0, 2, (B,), dtype=torch.uint8, device=dev)
     rrc = torch.from_numpy(RrcSampler(True, (0.08, 1.0), (3 / 4, 4 / 3), S, S, 1).draw(B)).to(dev)
-    for kind, kw in (("none", {"crop_offset": (7, 13)}), ("rrc", {"rrc": rrc})) * 2:
+    engines = {}            # one engine per antialias value, alternated between the cases
+    for aa in antialias:
+        engines[aa] = eng = HipEngine(ParamLayout(), B, crop=CROP, image_size=S, antialias=aa)
+        eng.init(seed=0)
+        engines[aa] = (eng, make_optimizer("adam", eng, lr=1e-3))
+    cases = [("none", False, {"crop_offset": (7, 13)})] if len(antialias) == 1 else []
+    for kind, aa, kw in (cases + [("rrc" + (" antialias" if aa else ""), aa, {"rrc": rrc}) for aa in antialias]) * 2:
+        eng, opt = engines[aa]
+
         def step():
             eng.forward_backward(img, lab, 1.0 / B, flip=flip, **kw)
             opt.step()
@@ -94,6 +136,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 2560])
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--antialias", action="store_true", help="the antialias rows (large sources) instead")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     text = []
@@ -103,9 +146,12 @@ def main():
         text.append(ln)
         print(ln, flush=True)
     emit(f"# bench/rrc.py on {torch.cuda.get_device_name(0)}; HBM peak taken as {HBM_PEAK / 1e12:.2f} TB/s")
-    kernel_rows(a.batches, emit)
+    if a.antialias:
+        antialias_rows(a.batches, emit)
+    else:
+        kernel_rows(a.batches, emit)
     if not a.no_step:
-        step_rows(emit)
+        step_rows(emit, *((448, (False, True)) if a.antialias else ()))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -498,7 +498,7 @@ void wgrad_f32(Tensor x, int64_t R, int64_t S, int64_t stride, int64_t pad, Tens
 }
 
 void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_t oy, int64_t ox, Tensor out,
-              OptT crop_dev, OptT mix, OptT rrc) {
+              OptT crop_dev, OptT mix, OptT rrc, bool antialias) {
   pddl::StemParams p{};
   PCHECK(in.is_cuda() && in.is_contiguous() && in.dim() == 4 && in.size(3) == 3, "stem input must be [B,H,W,3]");
   PCHECK(in.scalar_type() == torch::kUInt8 || in.scalar_type() == torch::kFloat32, "stem input uint8 or fp32");
@@ -522,6 +522,7 @@ void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_
            rrc->size(1) == 4 && rrc->size(0) >= p.B, "rrc: contiguous device int32 [>= B][4]");
     p.rrc = rrc->data_ptr<int32_t>();
     p.mode = 3;
+    p.antialias = antialias ? 1 : 0;   // (ignored without a box table)
   }
   p.scale = 1.f / 255.f;
   p.Hs = (int)((Hc + 6) / 2); p.Ws = (int)((Wc + 6) / 2);
@@ -973,10 +974,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_f32", &wgrad_f32, REL);
   m.def("stem_s2d", &stem_s2d, REL, py::arg("images"), py::arg("flip"), py::arg("mode"), py::arg("Hc"), py::arg("Wc"),
         py::arg("oy"), py::arg("ox"), py::arg("out"), py::arg("crop_dev"), py::arg("mix") = py::none(),
-        py::arg("rrc") = py::none());
-  // (kernel tests) what the last stem_s2d launch ran: ("pixel" | "rows" | "band", s2d rows per band workgroup)
+        py::arg("rrc") = py::none(), py::arg("antialias") = false);
+  // (kernel tests) what the last stem_s2d launch ran: ("pixel" | "rows" | "band" | "aa_band" | "aa_pixel",
+  // s2d rows per band workgroup)
   m.def("stem_last_launch", []() {
-    static const char* const form[] = {"pixel", "rows", "band"};
+    static const char* const form[] = {"pixel", "rows", "band", "aa_band", "aa_pixel"};
     int f = 0, band = 0;
     pddl::stem_last_launch(&f, &band);
     return py::make_tuple(form[f], band);

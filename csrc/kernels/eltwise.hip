@@ -43,7 +43,7 @@ __device__ __forceinline__ float stem_pix(const StemParams& p, int b, int y, int
   return v * p.scale;
 }
 
-// (StemMix, stem_mix_row / _weight / _blend: stem_common.h, shared with stem_rrc.hip)
+// (StemMix, stem_mix_row / _weight / _blend: stem_common.h, shared with stem_rrc.hip and stem_aa.hip)
 template <bool MIX>
 __device__ __forceinline__ float stem_val(const StemParams& p, const StemMix& m, float w, int b, int y, int x, int c) {
   if (!MIX) return stem_pix(p, b, y, x, c);

@@ -203,10 +203,11 @@ struct StemParams {
   uint16_t* out; int Hs, Ws;          // space-to-depth image [B][Hs][Ws][16], Hs = (Hc + 6) / 2
   const int32_t* mix;                 // optional mixup / CutMix table [B][8] (below); null: no mixing
   const int32_t* rrc;                 // mode 3: the random-resized-crop box table [B][4] (below)
+  int antialias;                      // mode 3: a box side that is shrunk takes a triangle filter (below)
 };
 // The per-image box table of mode 3, int32 [B][4], row b = {y0, x0, h, w}: a box of the Hin x Win
 // source in whole pixels that becomes image b's Hc x Wc picture (crop, then bilinear resize with
-// half-pixel centres, taps clamped to the box, no antialias).  The kernels clamp a row to
+// half-pixel centres, taps clamped to the box; no antialias unless `antialias`).  The kernels clamp a row to
 // y0 = clamp(y0, 0, Hin - 1), h = clamp(h, 1, Hin - y0) (likewise in x): a bad table gives a wrong
 // picture, never a stray read.  Output row y reads box rows clamp(ty, 0, h-1), clamp(ty+1, 0, h-1)
 // with ty = floor(((2y+1)h - Hc) / 2Hc) and the weight fy = (((2y+1)h - Hc) - ty 2Hc) / 2Hc, all
@@ -214,6 +215,20 @@ struct StemParams {
 // fp32 on the raw 0..255 values, horizontal first: top = fma(b - a, fx, a), bot = fma(d - c, fx, c),
 // v = fma(bot - top, fy, top) * scale.  {0, 0, Hc, Wc} is bitwise mode 0, {oy, ox, Hc, Wc} mode 2.
 // The mix table's box stays in the preprocessed image; the partner is resampled with its own row.
+// `antialias` (mode 3 only; ignored without a box table; stem_aa.hip).  Each axis on its own: a box
+// side of n source pixels resampled to N outputs, output index o (in x the flipped output column).
+//   n <= N: exactly the arithmetic above on that axis (rrc_tap / rrc_lerp), so a box that is not
+//           shrunk on either axis is bit for bit the picture without the flag.
+//   n > N:  a triangle filter of half-width n / N source pixels, in integers: box pixel i in
+//           [0, n-1] has weight u_i = 2n - |(2i+1) N - (2o+1) n| and is a tap when u_i > 0; D is the
+//           sum of u_i over the taps (taps outside the box are dropped, the rest renormalised by D;
+//           at least one and at most floor(2n / N) + 1 taps).
+// Horizontal pass first, per tapped row: uint8 input, S = sum u_i p_i as an integer (exact),
+// h = fdiv_rn(float(S), float(D)); fp32 input, S = fma(float(u_i), p_i, S) over ascending i from 0,
+// divided the same way.  Vertical pass over the h of the tapped rows, ascending k from acc = 0:
+// acc = fma(float(u_k), h_k, acc), v = fdiv_rn(acc, float(D_y)) * scale.  With one axis shrunk the
+// other keeps its lerp: h = fma(b - a, fx, a), or v = fma(bot - top, fy, top) * scale.  The launcher
+// returns an error string when S or the weight arithmetic could overflow int32 for the source.
 // The per-image mix table, int32 [B][8], shared by the stem kernels and the training heads.  Row b:
 //   0      partner: index in this batch of the image mixed into image b
 //   1..4   y0, x0, y1, x1: half-open box in the Hc x Wc preprocessed image (after each image's own
@@ -230,8 +245,12 @@ const char* stem_s2d_f32_launch(const StemParams& p, float* out, hipStream_t s);
 // Mode 3 (stem_rrc.hip; both launchers above forward to it): the band form for uint8 input whose
 // worst-case box fits the LDS budget, else the per-pixel form; out is bf16 or (out_f32) fp32.
 const char* stem_rrc_launch(const StemParams& p, void* out, int out_f32, hipStream_t s);
+// Mode 3 with `antialias` (stem_aa.hip; stem_rrc_launch forwards to it): likewise a band form and a
+// per-pixel form.
+const char* stem_aa_launch(const StemParams& p, void* out, int out_f32, hipStream_t s);
 // What the calling thread's last stem_s2d launch ran (tests): form 0 per-pixel, 1 row form, 2 band
-// form, and the band form's s2d rows per workgroup; kept per thread, since replicas launch from several.
+// form, 3 antialias band form, 4 antialias per-pixel form, and a band form's s2d rows per
+// workgroup; kept per thread, since replicas launch from several.
 void stem_note_launch(int form, int band);
 void stem_last_launch(int* form, int* band);
 extern int g_stem_rrc_band;   // tuning knob like g_stem_variant: > 0 caps the band height

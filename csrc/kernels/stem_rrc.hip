@@ -1,6 +1,6 @@
 // Random-resized-crop stem (gfx950): mode 3 of stem_s2d.  Image b's picture is the box
 // rrc[b] = {y0, x0, h, w} of its source, resized to Hc x Wc (bilinear, half-pixel centres, taps
-// clamped to the box, no antialias), then flipped, mixed, zero-padded and 2x2 space-to-depth'ed
+// clamped to the box, no antialias: that is stem_aa.hip), then flipped, mixed, zero-padded and 2x2 space-to-depth'ed
 // like the other modes.  The definition is in kernels.h (StemParams::rrc); its arithmetic is
 // rrc_box / rrc_tap / rrc_lerp below, which both kernel forms call, so the forms agree bit for bit.
 //
@@ -27,37 +27,7 @@
 
 namespace pddl {
 
-struct RrcBox { int y0, x0, h, w; };
-__device__ __forceinline__ RrcBox rrc_box(const StemParams& p, int b) {
-  const int32_t* r = p.rrc + (long)b * 4;
-  RrcBox q;
-  q.y0 = min(max(r[0], 0), p.Hin - 1); q.x0 = min(max(r[1], 0), p.Win - 1);
-  q.h = min(max(r[2], 1), p.Hin - q.y0); q.w = min(max(r[3], 1), p.Win - q.x0);
-  return q;
-}
-// Output index o of N along a box side of n source pixels: the two taps (box-relative) and the weight.
-struct RrcTap { int t0, t1; float f; };
-__device__ __forceinline__ RrcTap rrc_tap(int o, int n, int N) {
-  const int den = 2 * N, num = (2 * o + 1) * n - N;   // num > -den: the quotient below is floor(num / den)
-  const int t = (num + den) / den - 1;
-  RrcTap r;
-  r.f = __fdiv_rn((float)(num - t * den), (float)den);
-  r.t0 = min(max(t, 0), n - 1); r.t1 = min(max(t + 1, 0), n - 1);
-  return r;
-}
-__device__ __forceinline__ float rrc_lerp(float a, float b, float f) { return __fmaf_rn(b - a, f, a); }
-
-template <typename OutT> __device__ __forceinline__ void rrc_store(OutT* out, long q, const float* v);
-template <> __device__ __forceinline__ void rrc_store<uint16_t>(uint16_t* out, long q, const float* v) {
-  uint4* o = reinterpret_cast<uint4*>(out + q * 16);
-  o[0] = pack8(v);
-  o[1] = pack8(v + 8);
-}
-template <> __device__ __forceinline__ void rrc_store<float>(float* out, long q, const float* v) {
-  float4* o = reinterpret_cast<float4*>(out + q * 16);
-#pragma unroll
-  for (int d = 0; d < 4; ++d) o[d] = make_float4(v[d * 4], v[d * 4 + 1], v[d * 4 + 2], v[d * 4 + 3]);
-}
+// (RrcBox, rrc_box, rrc_tap, rrc_lerp, rrc_store: stem_common.h, shared with stem_aa.hip)
 
 // ------------------------------------------------------------------------------ per-pixel form
 // One image's view of s2d pixel (i, j): its box's first pixel and the taps of the two picture rows
@@ -291,6 +261,7 @@ static const char* stem_rrc_go(const StemParams& p, OutT* out, hipStream_t s) {
 }
 
 const char* stem_rrc_launch(const StemParams& p, void* out, int out_f32, hipStream_t s) {
+  if (p.antialias) return stem_aa_launch(p, out, out_f32, s);   // triangle-filter forms: stem_aa.hip
   return out_f32 ? stem_rrc_go<float>(p, reinterpret_cast<float*>(out), s)
                  : stem_rrc_go<uint16_t>(p, reinterpret_cast<uint16_t*>(out), s);
 }

@@ -25,7 +25,7 @@ def _banner(cfg, strategy):
           f"skip_nonfinite={cfg.skip_nonfinite}, "
           f"mixup={cfg.mixup:g}, cutmix={cfg.cutmix:g}, mix_prob={cfg.mix_prob:g}, "
           f"rrc={cfg.rrc}, rrc_scale={cfg.rrc_scale[0]:g}-{cfg.rrc_scale[1]:g}, "
-          f"rrc_ratio={cfg.rrc_ratio[0]:g}-{cfg.rrc_ratio[1]:g}", flush=True)
+          f"rrc_ratio={cfg.rrc_ratio[0]:g}-{cfg.rrc_ratio[1]:g}, antialias={cfg.antialias}", flush=True)
 
 
 def model_summary(cfg) -> str:
@@ -146,7 +146,8 @@ def _evaluate(cfg, strategy, trainer) -> int:
               f"{m['top5_accuracy']:.4f} - {m['images']} images - {m['images'] / dt:.1f} img/s", flush=True)
         if cfg.metrics_jsonl:
             rec = {"evaluate": True, **m, "images_per_sec": m["images"] / dt,
-                   "replicas": strategy.num_replicas_in_sync, "label_smoothing": cfg.label_smoothing}
+                   "replicas": strategy.num_replicas_in_sync, "label_smoothing": cfg.label_smoothing,
+                   "antialias": bool(cfg.antialias)}
             with open(cfg.metrics_jsonl, "a") as f:
                 f.write(json.dumps(rec) + "\n")
     _leave_process_group()

@@ -59,6 +59,8 @@ class TrainConfig:
                                                    # `crop` in the preprocess kernel) instead of RandomCrop
     rrc_scale: Tuple[float, float] = (0.08, 1.0)   # the box's area as a fraction of the image, uniform
     rrc_ratio: Tuple[float, float] = (3 / 4, 4 / 3)   # its aspect ratio w / h, log-uniform
+    antialias: bool = False                        # additive: a box side that is shrunk is resampled with a triangle
+                                                   # filter (--rrc boxes, and the evaluation resize at image_size > crop)
     global_clipnorm: Optional[float] = None        # additive (Keras `global_clipnorm`): the whole gradient is scaled
                                                    # by C / max(|g|, C) before the update; None = off
     skip_nonfinite: bool = False                   # additive: a step whose gradient norm is inf / nan updates nothing
@@ -241,8 +243,13 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="probability in [0, 1] that a training batch is mixed (default 1; needs --mixup or --cutmix)")
     a("--rrc", action="store_true", default=None,
       help="random-resized-crop (the Inception / torchvision augmentation): each training image is a random box of "
-           "its source, resized to --crop inside the preprocess kernel (bilinear, no antialias); replaces the "
-           "per-batch RandomCrop offset")
+           "its source, resized to --crop inside the preprocess kernel (bilinear; with --antialias a shrunk box "
+           "side takes a triangle filter); replaces the per-batch RandomCrop offset")
+    a("--antialias", action="store_true", default=None,
+      help="antialiased resampling in the preprocess kernel, for sources much larger than the crop (--image-size "
+           "384-512): with --rrc a box side that is shrunk takes a triangle filter of half-width n/N source pixels "
+           "instead of two bilinear taps, and at image_size > crop validation and --evaluate resize the whole source "
+           "the same way")
     a("--rrc-scale", type=float, nargs=2, dest="rrc_scale", metavar=("LO", "HI"),
       help="the box's area as a fraction of the image, uniform in [LO, HI] (default 0.08 1.0)")
     a("--rrc-ratio", type=float, nargs=2, dest="rrc_ratio", metavar=("LO", "HI"),

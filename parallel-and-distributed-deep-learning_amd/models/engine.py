@@ -55,9 +55,20 @@ def _mix_kw(mix):
     return {} if mix is None else {"mix": mix}
 
 
-def _rrc_kw(rrc):
-    """The `rrc=` keyword of the stem launch: absent without a random-resized-crop box table."""
-    return {} if rrc is None else {"rrc": rrc}
+def _rrc_kw(rrc, antialias=False):
+    """The `rrc=` (and `antialias=`) keywords of the stem launch: absent without a box table."""
+    if rrc is None:
+        return {}
+    return {"rrc": rrc, "antialias": True} if antialias else {"rrc": rrc}
+
+
+def eval_boxes(antialias, batch, crop, image_size, device):
+    """--antialias: the constant whole-image box table [batch][4] through which evaluation resizes a
+    source larger than the crop (the antialias kernel in place of stem mode 1); None otherwise."""
+    if not antialias or image_size <= crop:
+        return None
+    from ..train.rrc import full_table
+    return torch.from_numpy(full_table(batch, image_size, image_size)).to(device)
 
 
 class HipEngine(SideStream):
@@ -100,7 +111,12 @@ class HipEngine(SideStream):
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: int = 224,
                  device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, bitmask: Optional[bool] = None,
-                 grad_ring: Optional[int] = None, graphed=False, label_smoothing: float = 0.0):
+                 grad_ring: Optional[int] = None, graphed=False, label_smoothing: float = 0.0,
+                 antialias: bool = False):
+        # antialias: box tables are resampled by the triangle-filter stem kernel (a launch constant, like
+        # label_smoothing), and evaluation at image_size > crop goes through it with aa_full
+        self.antialias = bool(antialias)
+        self.aa_full = eval_boxes(antialias, batch, crop, image_size, device)
         # the loss of forward_backward, evaluate and evaluate_topk alike; a launch constant of the
         # head kernels, so a captured step keeps the value it was captured with
         self.label_smoothing = check_label_smoothing(label_smoothing)
@@ -592,7 +608,7 @@ class HipEngine(SideStream):
         if mode == 2 and isinstance(crop_offset, torch.Tensor):   # device offsets (graph capture)
             crop_dev, oy, ox = crop_offset, 0, 0
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
-                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else self.aa_full, self.antialias))
         H1, H2, Hs = self.H1, self.H2, self.Hs
         s = L.stem
         pool = self.pool[:B]

@@ -202,7 +202,7 @@ class HipEngineBNTrain(HipEngine):
         if mode == 2 and isinstance(crop_offset, torch.Tensor):
             crop_dev, oy, ox = crop_offset, 0, 0
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, crop_dev,
-                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else self.aa_full, self.antialias))
         H1, Hs = self.H1, self.Hs
         s = L.stem
         zs = self.zs[:B]

@@ -29,7 +29,7 @@ import torch
 from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
-from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw, _rrc_kw
+from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw, _rrc_kw, eval_boxes
 from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
 from .side_stream import SideStream
 
@@ -47,8 +47,11 @@ class HipF32Engine(SideStream):
     BN_MODES = ("frozen",)
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
-                 device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, label_smoothing: float = 0.0):
+                 device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, label_smoothing: float = 0.0,
+                 antialias: bool = False):
         self.label_smoothing = check_label_smoothing(label_smoothing)   # the loss of every head call
+        self.antialias = bool(antialias)                                 # (HipEngine.__init__: the same two fields)
+        self.aa_full = eval_boxes(antialias, batch, crop, image_size if image_size is not None else crop, device)
         if bn_mode not in self.BN_MODES:
             raise ValueError(f"{type(self).__name__} runs bn_mode {self.BN_MODES[0]!r} "
                              "(HipF32Engine: frozen, the reference's training=False; HipF32EngineBNTrain: train)")
@@ -272,7 +275,7 @@ class HipF32Engine(SideStream):
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
-                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else self.aa_full, self.antialias))
         s = L.stem
         c1 = self.c1[:B]
         ch = self.ch[s.name]
@@ -482,9 +485,10 @@ class HipF32EngineBNTrain(HipF32Engine):
     RING = 12   # (fp32 b256: ring 3 / 5 / 8 / 12 / 16 -> 73.4 / 73.1 / 72.3-72.6 / 71.9 / 71.8 ms)
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
-                 device="cuda", bn_mode: str = "train", num_classes: int = 1000, label_smoothing: float = 0.0):
+                 device="cuda", bn_mode: str = "train", num_classes: int = 1000, label_smoothing: float = 0.0,
+                 antialias: bool = False):
         super().__init__(layout, batch, crop=crop, image_size=image_size, device=device, bn_mode=bn_mode,
-                         num_classes=num_classes, label_smoothing=label_smoothing)
+                         num_classes=num_classes, label_smoothing=label_smoothing, antialias=antialias)
         assert struct.calcsize(_STAT_FMT) == self.N.BNSTAT_LAYER_BYTES
         f32 = dict(dtype=torch.float32, device=self.device)
         n = self.nch
@@ -573,7 +577,7 @@ class HipF32EngineBNTrain(HipF32Engine):
         mode, oy, ox = self._stem_mode(training, crop_offset)
         x2 = self.x2[:B]
         N.stem_s2d(images, flip if training else None, mode, self.crop, self.crop, oy, ox, x2, None,
-                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else None))
+                   **_mix_kw(mix if training else None), **_rrc_kw(rrc if training else self.aa_full, self.antialias))
         s = L.stem
         zs, c1 = self.zs[:B], self.c1[:B]
         self._z(s, x2, 4, 1, 0, self.H1, self.wf32[:64 * STEM_K].view(64, STEM_K), zs, training)

@@ -91,15 +91,70 @@ def rrc_resample(images: torch.Tensor, rrc: torch.Tensor, Hc: int, Wc: int, flip
     return ((top + (bot - top) * fy) * (1.0 / 255.0)).permute(0, 3, 1, 2)
 
 
+def aa_weights(o: torch.Tensor, n: torch.Tensor, N: int, size: int) -> torch.Tensor:
+    """The triangle-filter weights of the antialias definition (kernels.h, `StemParams::antialias`),
+    int64 [B][N][size]: u_i = 2n - |(2i+1) N - (2o+1) n| of box pixel i for output index o [B][N] along
+    box sides of n [B] pixels; 0 where i is no tap (u_i <= 0 or i >= n)."""
+    i = torch.arange(size, device=o.device).view(1, 1, size)
+    n = n.view(-1, 1, 1)
+    u = 2 * n - ((2 * i + 1) * N - (2 * o.unsqueeze(-1) + 1) * n).abs()
+    return u.clamp_min(0) * (i < n)
+
+
+def aa_resample(images: torch.Tensor, rrc: torch.Tensor, Hc: int, Wc: int, flip: Optional[torch.Tensor] = None):
+    """rrc_resample with the antialias flag: an axis whose box side is not shrunk keeps rrc_resample's
+    two taps; a shrunk one takes the triangle filter, horizontal pass first (the weighted sum is
+    exact for uint8 input, then one fp32 division), then the vertical pass over its fp32 results.
+    A CPU reference for small images: it gathers the whole box-relative source and multiplies dense
+    [B][N][size] weight matrices, and its sums are matrix products, not the definition's ascending
+    fma chains, so it agrees with the kernels to rounding (2T + 6 roundings), not bit for bit."""
+    B, H, W, _ = images.shape
+    dev = images.device
+    t = rrc[:B].to(dev).long()
+    y0, x0 = t[:, 0].clamp(0, H - 1), t[:, 1].clamp(0, W - 1)
+    h, w = torch.minimum(t[:, 2].clamp_min(1), H - y0), torch.minimum(t[:, 3].clamp_min(1), W - x0)
+    ys = torch.arange(Hc, device=dev).expand(B, Hc)
+    xs = torch.arange(Wc, device=dev).expand(B, Wc)
+    if flip is not None:
+        xs = torch.where(flip.to(dev).bool().view(B, 1), Wc - 1 - xs, xs)
+    bi = torch.arange(B, device=dev).view(B, 1, 1)
+    # the box's pixels at box-relative indices (indices past the box read the edge; no tap uses them)
+    src = images.float()[bi, (y0.view(B, 1) + torch.arange(H, device=dev)).clamp_max(H - 1).view(B, H, 1),
+                         (x0.view(B, 1) + torch.arange(W, device=dev)).clamp_max(W - 1).view(B, 1, W)]   # [B,H,W,3]
+    bh = torch.arange(B, device=dev).view(B, 1, 1)
+    # horizontal: [B,H,Wc,3]
+    xa, xb, fx = rrc_taps(xs, w, Wc)
+    a, b = src[bh, torch.arange(H, device=dev).view(1, H, 1), xa.view(B, 1, Wc)], \
+        src[bh, torch.arange(H, device=dev).view(1, H, 1), xb.view(B, 1, Wc)]
+    lerp_x = a + (b - a) * fx.view(B, 1, Wc, 1)
+    ux = aa_weights(xs, w, Wc, W).double()                                          # [B,Wc,W]
+    S = torch.einsum("bxj,bijc->bixc", ux, src.double()).float()                    # (exact for integer pixels)
+    filt_x = S / ux.sum(-1).float().view(B, 1, Wc, 1)
+    hx = torch.where((w > Wc).view(B, 1, 1, 1), filt_x, lerp_x)
+    # vertical: [B,Hc,Wc,3]
+    ya, yb, fy = rrc_taps(ys, h, Hc)
+    top, bot = hx[bh, ya.view(B, Hc, 1), torch.arange(Wc, device=dev).view(1, 1, Wc)], \
+        hx[bh, yb.view(B, Hc, 1), torch.arange(Wc, device=dev).view(1, 1, Wc)]
+    lerp_y = top + (bot - top) * fy.view(B, Hc, 1, 1)
+    uy = aa_weights(ys, h, Hc, H).float()                                           # [B,Hc,H]
+    filt_y = torch.einsum("byi,bixc->byxc", uy, hx) / uy.sum(-1).view(B, Hc, 1, 1)
+    v = torch.where((h > Hc).view(B, 1, 1, 1), filt_y, lerp_y)
+    return (v * (1.0 / 255.0)).permute(0, 3, 1, 2)
+
+
 def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[torch.Tensor] = None,
                crop_offset=(0, 0), mix: Optional[torch.Tensor] = None,
-               rrc: Optional[torch.Tensor] = None) -> torch.Tensor:
+               rrc: Optional[torch.Tensor] = None, antialias: bool = False) -> torch.Tensor:
     """[B,H,W,3] uint8/float (0..255) -> NCHW float32 in [0,1] at crop x crop.  mix (training
     only): a mixup / CutMix table, applied after each image's own crop and flip.  rrc (training
-    only): a random-resized-crop box table, which replaces the crop / resize."""
+    only): a random-resized-crop box table, which replaces the crop / resize.  antialias: box tables
+    are resampled with the triangle filter, and so is the evaluation resize of a larger source."""
     if training and rrc is not None:
-        x = rrc_resample(images, rrc, crop, crop, flip)
+        x = (aa_resample if antialias else rrc_resample)(images, rrc, crop, crop, flip)
         return mix_pixels(x, mix) if mix is not None else x
+    if not training and antialias and crop < images.shape[1]:
+        from ..train.rrc import full_table
+        return aa_resample(images, torch.from_numpy(full_table(images.shape[0], *images.shape[1:3])), crop, crop)
     x = images.float().permute(0, 3, 1, 2) * (1.0 / 255.0)
     H, W = x.shape[-2:]
     if crop > H or crop > W or (not training and crop != H):
@@ -280,8 +335,9 @@ class TorchEngine:
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, device="cpu", bn_mode="frozen",
                  num_classes: int = 1000, bf16_points: bool = False, fused_proj: bool = False,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, antialias: bool = False):
         self.L = layout
+        self.antialias = bool(antialias)
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.device = torch.device(device)
         self.batch = batch
@@ -307,7 +363,7 @@ class TorchEngine:
         p = self.params[: self.L.n_trainable].clone().requires_grad_(True)
         self.model.stats = self.params
         self.model.bind(p)
-        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix, rrc)
+        x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix, rrc, self.antialias)
         logits = self.model.logits(p, x, training=True)
         lab = counted = labels.to(self.device)
         if mix is not None:
@@ -330,7 +386,7 @@ class TorchEngine:
 
     @torch.no_grad()
     def evaluate(self, images, labels):
-        x = preprocess(images.to(self.device), self.crop, False)
+        x = preprocess(images.to(self.device), self.crop, False, antialias=self.antialias)
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)
@@ -342,7 +398,7 @@ class TorchEngine:
         """[loss sum, top-1 hits, top-k hits].  rank = #{j : logit[j] > logit[label] or (logit[j] ==
         logit[label] and j < label)}: equal logits are ordered by index, so rank == 0 is
         evaluate's "first argmax == label"; a top-k hit is rank < k."""
-        x = preprocess(images.to(self.device), self.crop, False)
+        x = preprocess(images.to(self.device), self.crop, False, antialias=self.antialias)
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)

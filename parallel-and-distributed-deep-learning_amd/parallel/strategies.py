@@ -89,16 +89,16 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
         return make_hip_engine(L, cap, bn_mode=cfg.bn_mode, crop=cfg.crop, image_size=cfg.image_size,
                                device=device, num_classes=cfg.num_classes,
                                grad_ring=HipEngine.GRAD_RING if graphed else None, graphed=graphed,
-                               label_smoothing=cfg.label_smoothing)
+                               label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
     if device.type == "cuda":
         from ..models.engine_f32 import HipF32Engine, HipF32EngineBNTrain
         # frozen: the reference's configuration; train: batch statistics (both explicit fp32 schedules)
         cls = HipF32Engine if cfg.bn_mode == "frozen" else HipF32EngineBNTrain
         return cls(L, cap, crop=cfg.crop, image_size=cfg.image_size, device=device, num_classes=cfg.num_classes,
-                   label_smoothing=cfg.label_smoothing)
+                   label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
     from ..models.reference import TorchEngine
     return TorchEngine(L, cap, crop=cfg.crop, device=device, bn_mode=cfg.bn_mode, num_classes=cfg.num_classes,
-                       label_smoothing=cfg.label_smoothing)
+                       label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
 
 
 class Augment:

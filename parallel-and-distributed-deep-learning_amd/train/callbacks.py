@@ -237,6 +237,7 @@ class JsonlLogger(Callback):
         rec["rrc"] = bool(getattr(self.trainer.cfg, "rrc", False))
         rec["rrc_scale"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_scale", (0.08, 1.0))]
         rec["rrc_ratio"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_ratio", (3 / 4, 4 / 3))]
+        rec["antialias"] = bool(getattr(self.trainer.cfg, "antialias", False))
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)

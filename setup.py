@@ -31,10 +31,11 @@ HIP_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-ffp-contract=fast"
 # A/B builds of compile-time kernel parameters, e.g. PDDL_HIP_DEFINES="-DIGEMM_MIN_BLOCKS_1=4"
 # (use a separate PDDL_BUILD_TEMP: objects are rebuilt on source changes only)
 HIP_FLAGS += os.environ.get("PDDL_HIP_DEFINES", "").split()
-# Per-file flags.  stem_rrc.hip is compiled without the packed-fp32 VALU forms (v_pk_fma_f32,
+# Per-file flags.  stem_rrc.hip and stem_aa.hip are compiled without the packed-fp32 VALU forms (v_pk_fma_f32,
 # v_pk_mul_f32, v_pk_add_f32).  The kernels are memory-bound: built with and without the flag they
 # pass the same tests and take the same time (profiles/rrc.txt), so the plainer code costs nothing.
-FILE_FLAGS = {"stem_rrc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"stem_rrc.hip": NO_PK_F32, "stem_aa.hip": NO_PK_F32}
 
 
 def compile_kernels():
