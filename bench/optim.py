@@ -1,7 +1,9 @@
 """Fused optimizer steps over the flat parameter buffer (ParamLayout().n_trainable floats): adam,
-sgd and lars as the training step launches them (the one-thread hparams kernel + the update;
-lars: + the norm pass), µs per step and achieved GB/s.  adam and lars move the same bytes
-(adam: p, g, m, v read, p, m, v written; lars: p, g read, then p, g, v read and p, v written).
+sgd, lars and lamb as the training step launches them (the one-thread hparams kernel + the update;
+lars: + the norm pass; lamb: the moment pass + the update pass), µs per step and achieved GB/s.
+adam and lars move the same bytes (adam: p, g, m, v read, p, m, v written; lars: p, g read, then
+p, g, v read and p, v written); lamb moves 10 floats per parameter (p, g, m, v read and m, v
+written, then p, m, v read and p written).
 With --clip C every optimizer is also timed with global-norm clipping at C (`*_clip_us`: the norm
 pass + the update reading the device scale) and the norm pass alone (`grad_norm_us`, GB/s over
 the 4 n bytes it reads).
@@ -18,9 +20,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import pddl  # noqa: E402,F401
 from pddl.models.resnet50 import ParamLayout  # noqa: E402
-from pddl.train.optim import LARS, make_optimizer  # noqa: E402
+from pddl.train.optim import LAMB, LARS, make_optimizer  # noqa: E402
 
-FLOATS_MOVED = {"adam": 7, "sgd": 5, "lars": 7}   # per parameter, reads + writes
+FLOATS_MOVED = {"adam": 7, "sgd": 5, "lars": 7, "lamb": 10}   # per parameter, reads + writes
 
 
 class FlatEngine:
@@ -46,7 +48,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--chunk", type=int, default=None, help="lars: floats per block (default: the kernel's)")
+    ap.add_argument("--chunk", type=int, default=None, help="lars, lamb: floats per block (default: the kernel's)")
     ap.add_argument("--clip", type=float, default=None, help="also time every optimizer with --global-clipnorm C")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -54,11 +56,13 @@ def main():
     eng = FlatEngine(L, "cuda")
     n = L.n_trainable
     res = {"n": n}
-    for name in ("adam", "sgd", "lars"):
+    for name in ("adam", "sgd", "lars", "lamb"):
         # a tiny rate: hundreds of timed steps must not blow the parameters up
         if name == "lars":
             opt = LARS(eng, lr=1e-6, momentum=0.9, weight_decay=5e-5, chunk=a.chunk)
             res["lars_chunk"] = opt.chunk
+        elif name == "lamb":
+            opt = LAMB(eng, lr=1e-6, weight_decay=5e-5, chunk=a.chunk)
         else:
             opt = make_optimizer(name, eng, lr=1e-6)
         runs = sorted(timeit(opt.step, a.iters) for _ in range(a.repeats))
@@ -86,6 +90,8 @@ def main():
                 res["grad_norm_GBps"] = round(4 * n / us / 1e3)
         del opt
     res["lars_over_adam"] = round(res["lars_us"] / res["adam_us"], 3)
+    res["lamb_over_adam"] = round(res["lamb_us"] / res["adam_us"], 3)
+    res["lamb_over_lars"] = round(res["lamb_us"] / res["lars_us"], 3)
     print(json.dumps(res), flush=True)
     if a.json:
         json.dump(res, open(a.json, "w"), indent=1)

@@ -823,6 +823,34 @@ void lars(Tensor p, Tensor g, Tensor mom, Tensor table, Tensor table_host, int64
                        gnp(gn), cur_stream()),
      "lars");
 }
+// Adam with a per-layer trust ratio and decoupled weight decay (kernels.h); the table, partials
+// and ratios are those of lars.  t and lr are used only when hs is not given.
+void lamb(Tensor p, Tensor g, Tensor m, Tensor v, Tensor table, Tensor table_host, int64_t chunk, Tensor partials,
+          Tensor ratios, double lr, double t, double b1, double b2, double eps, double wd, double gscale, OptT hs,
+          OptT gn) {
+  int64_t nseg;
+  const pddl::LarsSeg* segs = lars_host_table(table_host, nseg);
+  PCHECK(table.is_cuda() && table.scalar_type() == torch::kInt32 && table.is_contiguous() &&
+             table.numel() == table_host.numel(),
+         "lamb: device table is the int32 GPU copy of the host table");
+  PCHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous() &&
+             g.numel() >= p.numel() && m.numel() >= p.numel() && v.numel() >= p.numel() && p.numel() <= INT32_MAX,
+         "lamb: p, g, m, v contiguous, g, m and v at least as long as p");
+  PCHECK(partials.is_contiguous() && ratios.is_contiguous() && chunk > 0 && chunk <= INT32_MAX, "lamb: buffers");
+  PCHECK(!hs.has_value() || hs->numel() >= 3, "lamb: hs is device float[>=3]");
+  for (const Tensor* x : {&g, &m, &v, &table, &partials, &ratios})
+    PCHECK(x->device() == p.device(), "lamb: every buffer on the device of p");
+  PCHECK((!hs.has_value() || hs->device() == p.device()) && (!gn.has_value() || gn->device() == p.device()),
+         "lamb: hs and gn on the device of p");
+  for (const Tensor* x : {&p, &g, &m, &v})
+    PCHECK(reinterpret_cast<uintptr_t>(x->data_ptr()) % 16 == 0, "lamb: p, g, m, v 16-byte aligned");
+  PCHECK(reinterpret_cast<uintptr_t>(partials.data_ptr()) % 8 == 0, "lamb: partials 8-byte aligned");
+  ok(pddl::lamb_launch(f32p(p), f32p(g), f32p(m), f32p(v), p.numel(),
+                       reinterpret_cast<const pddl::LarsSeg*>(table.data_ptr()), segs, (int)nseg, (int)chunk,
+                       f32p(partials), partials.numel(), f32p(ratios), ratios.numel(), (float)lr, (float)t, (float)b1,
+                       (float)b2, (float)eps, (float)wd, (float)gscale, of32p(hs), gnp(gn), cur_stream()),
+     "lamb");
+}
 // Global norm of gscale * g into gn[0], the clip scale into gn[1], the skip flag into gn[2] (kernels.h).
 void grad_norm(Tensor g, double gscale, int64_t chunk, Tensor partials, Tensor gn) {
   PCHECK(g.is_contiguous() && partials.is_contiguous() && gn.is_contiguous() && gn.numel() >= 8 &&
@@ -1047,6 +1075,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     else if (which == "bn_red_blocks") pddl::g_bn_red_blocks = v;
     else if (which == "bn_apply_blocks") pddl::g_bn_apply_blocks = v;
     else if (which == "pool_blocks") pddl::g_pool_blocks = v;
+    else if (which == "lamb_reverse") pddl::g_lamb_reverse = v;
     else if (which == "colred_chunks") { TORCH_CHECK(v >= 1 && v <= 65535, "colred_chunks"); pddl::g_colred_chunks = v; }
     else TORCH_CHECK(false, "unknown kernel knob ", which);
   });
@@ -1152,6 +1181,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lars", &lars, REL, py::arg("p"), py::arg("g"), py::arg("momentum"), py::arg("table"), py::arg("table_host"),
         py::arg("chunk"), py::arg("partials"), py::arg("ratios"), py::arg("lr"), py::arg("mu"), py::arg("wd"),
         py::arg("eta"), py::arg("eps"), py::arg("gscale"), py::arg("hs") = none, py::arg("gn") = none);
+  m.def("lamb", &lamb, REL, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("table"),
+        py::arg("table_host"), py::arg("chunk"), py::arg("partials"), py::arg("ratios"), py::arg("lr"), py::arg("t"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("gscale"), py::arg("hs") = none,
+        py::arg("gn") = none);
   m.def("grad_norm", &grad_norm, REL, py::arg("g"), py::arg("gscale"), py::arg("chunk"), py::arg("partials"),
         py::arg("gn"));
   m.attr("GRAD_NORM_DEFAULT_CHUNK") = (int)pddl::kGradNormDefaultChunk;

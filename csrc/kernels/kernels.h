@@ -484,6 +484,15 @@ const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSe
                         int nseg, int chunk, float* partials, long partials_floats, float* ratios, long ratios_floats,
                         float lr, float momentum, float wd, float eta, float eps, float gscale, const float* hs,
                         const float* gn, hipStream_t s);
+// LAMB over the same table: m, v are Adam's slots, partials[chunk0 + c] = (sum w^2, sum u^2) of the
+// update direction u, ratios[s] = |w| / |u| (1 for adapt = 0, which also takes no decay).  The
+// step count comes from hs[0] and the rate from hs[2] (hparams kernel with adam = 0), or from t
+// and lr when hs is null.  The gradient buffer is only read.
+extern int g_lamb_reverse;   // tuning knob (A/B timing): pass 2 walks the chunks last to first
+const char* lamb_launch(float* p, const float* g, float* m, float* v, long n, const LarsSeg* segs_dev,
+                        const LarsSeg* segs_host, int nseg, int chunk, float* partials, long partials_floats,
+                        float* ratios, long ratios_floats, float lr, float t, float b1, float b2, float eps, float wd,
+                        float gscale, const float* hs, const float* gn, hipStream_t s);
 // Global gradient norm for clipping and the non-finite skip.  Chunk b = floats [b chunk, (b + 1) chunk)
 // of g is summed by block b into partials[b]; one block folds them and updates
 // gn[8] = {norm, scale, skip, clip, skip_enabled, clipped steps, skipped steps, -} (slots 3, 4 host-written).

@@ -9,7 +9,8 @@
 // p += mu v - lr g), with optional L2 weight decay folded into g.
 // One launch updates all 25.6M parameters; 16-byte loads/stores per lane.
 // LARS (large global batches) is momentum SGD with a per-layer trust ratio: two launches over a
-// segment table of the same buffer, a norm pass and an update pass (below).
+// segment table of the same buffer, a norm pass and an update pass (below).  LAMB is Adam under
+// the same per-layer rule, over the same table: a moment pass and an update pass.
 #include "common.h"
 #include "kernels.h"
 
@@ -244,6 +245,148 @@ __global__ __launch_bounds__(256) void lars_update_kernel(float* __restrict__ p,
   }
 }
 
+// ---- LAMB (You et al. 2019): Adam with a per-layer trust ratio and decoupled weight decay ----
+// Over the LARS segment table, under the LARS rule (above lars_find_seg): block b owns chunk b,
+// the norms come out of the same fixed tree, no atomics.  With c1 = 1 - b1^t, c2 = 1 - b2^t:
+//   g' = gs g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2
+//   u = (m / c1) / (sqrt(v / c2) + eps) + wd w;  ratio = |w| / |u|  (1 when not adapted or a norm is 0)
+//   w -= lr ratio u
+// |u| needs the new m and v of the whole segment, so the step is two launches.  Pass 1
+// (lamb_moment_kernel) reads p g m v, writes m v, forms u in registers and writes one
+// (sum w^2, sum u^2) pair per chunk.  Pass 2 (lamb_update_kernel) folds the segment's pairs,
+// re-reads p m v, rebuilds u from the stored m and v and writes p: 6 + 4 = 10 floats per
+// parameter, and the gradient buffer is only read (pass 2 needs neither g nor gs).  Both passes
+// get u from lamb_u below, whose operations are fixed one by one (no contraction, one explicit
+// fma), so pass 2 applies bit for bit the u whose norm pass 1 took.
+
+// 1 / (1 - b^t) for both betas, in double: t is the integer step count, so b^t is a product of
+// repeated squares (24 at most: t < 2^24), each rounded to 2^-53.  In fp32 1 - b2^t would lose
+// most of its bits at small t (see opt_hparams_sched_kernel).  One thread per block calls this.
+__device__ float2 lamb_bias_recip(float t, float b1, float b2) {
+  double r1 = 1.0, r2 = 1.0, q1 = b1, q2 = b2;
+  for (int k = (int)t; k > 0; k >>= 1) {
+    if (k & 1) { r1 *= q1; r2 *= q2; }
+    q1 *= q1;
+    q2 *= q2;
+  }
+  return make_float2((float)(1.0 / (1.0 - r1)), (float)(1.0 / (1.0 - r2)));
+}
+
+__device__ __forceinline__ float lamb_u(float w, float m, float v, float rc1, float rc2, float eps, float wd) {
+#pragma clang fp contract(off)
+  const float mh = m * rc1;
+  const float vh = v * rc2;
+  const float q = mh / (sqrtf(vh) + eps);
+  return __fmaf_rn(wd, w, q);
+}
+
+__global__ __launch_bounds__(256) void lamb_moment_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          const LarsSeg* __restrict__ segs, int nseg, int chunk,
+                                                          float2* __restrict__ partials, float t, float b1, float b2,
+                                                          float eps, float wd, float gs,
+                                                          const float* __restrict__ hs,
+                                                          const float* __restrict__ gn) {
+  __shared__ float2 red[4];
+  __shared__ float2 bias;
+  if (gn) {
+    if (gn[2] != 0.f) return;   // (skipped step: m, v and the partials stay; pass 2 returns as well)
+    gs *= gn[1];
+  }
+  if (threadIdx.x == 0) bias = lamb_bias_recip(hs ? hs[0] : t, b1, b2);
+  const int b = blockIdx.x;
+  const LarsSeg sg = segs[lars_find_seg(segs, nseg, b)];
+  if (!sg.adapt) wd = 0.f;   // biases and BN parameters: no decay, no adaptation
+  const long start = (long)(b - sg.chunk0) * chunk;
+  const int n4 = (int)lmin((long)chunk, sg.size - start) >> 2;
+  const float4* p4 = reinterpret_cast<const float4*>(p + sg.off + start);
+  const float4* g4 = reinterpret_cast<const float4*>(g + sg.off + start);
+  float4* m4 = reinterpret_cast<float4*>(m + sg.off + start);
+  float4* v4 = reinterpret_cast<float4*>(v + sg.off + start);
+  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+  __syncthreads();
+  const float rc1 = bias.x, rc2 = bias.y;
+  float sw = 0.f, su = 0.f;
+#pragma unroll 2
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const float4 w = p4[i];
+    const float4 gg = g4[i];
+    float4 mm = m4[i];
+    float4 vv = v4[i];
+    float4 u;
+#define LAMB1(c)                                              \
+  {                                                           \
+    const float gr = gg.c * gs;                               \
+    mm.c = __fmaf_rn(b1, mm.c, omb1 * gr);                    \
+    vv.c = __fmaf_rn(b2, vv.c, (omb2 * gr) * gr);             \
+    u.c = lamb_u(w.c, mm.c, vv.c, rc1, rc2, eps, wd);         \
+  }
+    LAMB1(x) LAMB1(y) LAMB1(z) LAMB1(w)
+#undef LAMB1
+    m4[i] = mm;
+    v4[i] = vv;
+    sw += (w.x * w.x + w.y * w.y) + (w.z * w.z + w.w * w.w);
+    su += (u.x * u.x + u.y * u.y) + (u.z * u.z + u.w * u.w);
+  }
+  const float2 r = lars_block_sum2(sw, su, red);
+  if (threadIdx.x == 0) partials[b] = r;   // (a non-adapted chunk's pair is never read)
+}
+
+// reverse = 1: block k takes chunk gridDim.x - 1 - k, so the lines pass 1 touched last are read
+// first.  Only the block -> chunk mapping flips: which partials a segment folds, and in which
+// order, is unchanged.
+__global__ __launch_bounds__(256) void lamb_update_kernel(float* __restrict__ p, const float* __restrict__ m,
+                                                          const float* __restrict__ v,
+                                                          const LarsSeg* __restrict__ segs, int nseg, int chunk,
+                                                          const float2* __restrict__ partials,
+                                                          float* __restrict__ ratios, float lr, float t, float b1,
+                                                          float b2, float eps, float wd, int reverse,
+                                                          const float* __restrict__ hs,
+                                                          const float* __restrict__ gn) {
+  __shared__ float2 red[4];
+  __shared__ float2 bias;
+  if (hs) lr = hs[2];
+  if (gn && gn[2] != 0.f) return;   // (the ratios of the last applied step stay)
+  if (threadIdx.x == 0) bias = lamb_bias_recip(hs ? hs[0] : t, b1, b2);
+  const int b = reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+  const int s = lars_find_seg(segs, nseg, b);
+  const LarsSeg sg = segs[s];
+  float ratio = 1.f;
+  if (sg.adapt) {
+    const int nc = (int)((sg.size + (long)chunk - 1) / chunk);
+    float sw = 0.f, su = 0.f;
+    for (int j = threadIdx.x; j < nc; j += 256) {
+      const float2 q = partials[sg.chunk0 + j];
+      sw += q.x;
+      su += q.y;
+    }
+    const float2 r = lars_block_sum2(sw, su, red);
+    const float wn = sqrtf(r.x), un = sqrtf(r.y);
+    if (wn > 0.f && un > 0.f) ratio = wn / un;
+  } else {
+    wd = 0.f;
+  }
+  if (b == sg.chunk0 && threadIdx.x == 0) ratios[s] = ratio;
+  const float nstep = -(lr * ratio);
+  const long start = (long)(b - sg.chunk0) * chunk;
+  const int n4 = (int)lmin((long)chunk, sg.size - start) >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p + sg.off + start);
+  const float4* m4 = reinterpret_cast<const float4*>(m + sg.off + start);
+  const float4* v4 = reinterpret_cast<const float4*>(v + sg.off + start);
+  __syncthreads();   // (bias: the non-adapted branch has met no barrier yet)
+  const float rc1 = bias.x, rc2 = bias.y;
+#pragma unroll 2
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 pp = p4[i];
+    const float4 mm = m4[i];
+    const float4 vv = v4[i];
+#define LAMB2(c) pp.c = __fmaf_rn(nstep, lamb_u(pp.c, mm.c, vv.c, rc1, rc2, eps, wd), pp.c);
+    LAMB2(x) LAMB2(y) LAMB2(z) LAMB2(w)
+#undef LAMB2
+    p4[i] = pp;
+  }
+}
+
 // ---- global-norm gradient clipping and non-finite skip ------------------------------------
 // The whole-buffer form of the LARS norm pass, under the same rule (above lars_find_seg):
 // replicas clip identical all-reduced gradients and nothing re-synchronises the parameters
@@ -417,6 +560,25 @@ const char* lars_launch(float* p, const float* g, float* v, long n, const LarsSe
                      reinterpret_cast<float2*>(partials), gn);
   hipLaunchKernelGGL(lars_update_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, v, segs_dev, nseg, chunk,
                      reinterpret_cast<const float2*>(partials), ratios, lr, momentum, wd, eta, eps, gscale, hs, gn);
+  LAUNCH_RET
+}
+int g_lamb_reverse = 1;   // pass 2 walks the chunks last to first: 8 % off the step (profiles/lamb_optim.txt)
+const char* lamb_launch(float* p, const float* g, float* m, float* v, long n, const LarsSeg* segs_dev,
+                        const LarsSeg* segs_host, int nseg, int chunk, float* partials, long partials_floats,
+                        float* ratios, long ratios_floats, float lr, float t, float b1, float b2, float eps, float wd,
+                        float gscale, const float* hs, const float* gn, hipStream_t s) {
+  const char* err;
+  const long chunks = lars_check_table(segs_host, nseg, n, chunk, &err);
+  if (chunks < 0) return err;
+  if (partials_floats < 2 * chunks) return "lamb: partials buffer smaller than 2 floats per chunk";
+  if (ratios_floats < nseg) return "lamb: ratio buffer smaller than the segment table";
+  if (!(b1 >= 0.f && b1 < 1.f && b2 >= 0.f && b2 < 1.f)) return "lamb: b1 and b2 must be in [0, 1)";
+  if (!hs && !(t >= 1.f && t < 16777216.f)) return "lamb: without hs the step count t must be in [1, 2^24)";
+  hipLaunchKernelGGL(lamb_moment_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, g, m, v, segs_dev, nseg, chunk,
+                     reinterpret_cast<float2*>(partials), t, b1, b2, eps, wd, gscale, hs, gn);
+  hipLaunchKernelGGL(lamb_update_kernel, dim3((unsigned)chunks), dim3(256), 0, s, p, m, v, segs_dev, nseg, chunk,
+                     reinterpret_cast<const float2*>(partials), ratios, lr, t, b1, b2, eps, wd, g_lamb_reverse ? 1 : 0,
+                     hs, gn);
   LAUNCH_RET
 }
 const char* grad_norm_launch(const float* g, long n, float gscale, int chunk, float* partials, long partials_floats,

@@ -11,7 +11,7 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import check_accum, check_clip, check_loss, check_mix, check_rrc, config_from_args
+from .config import check_accum, check_clip, check_layer_adapt, check_loss, check_mix, check_rrc, config_from_args
 
 
 def _banner(cfg, strategy):
@@ -20,7 +20,7 @@ def _banner(cfg, strategy):
           f"strategy={cfg.strategy}, replicas={strategy.num_replicas_in_sync}, "
           f"per-replica batch={strategy.per_replica_batch}, global batch={strategy.global_batch}, "
           f"accum_steps={cfg.accum_steps}, effective global batch={strategy.global_batch * cfg.accum_steps}, "
-          f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}, "
+          f"crop={cfg.crop}, bn={cfg.bn_mode}, optimizer={cfg.optimizer}, layer_adapt={cfg.layer_adapt}, "
           f"label_smoothing={cfg.label_smoothing:g}, global_clipnorm={cfg.global_clipnorm}, "
           f"skip_nonfinite={cfg.skip_nonfinite}, "
           f"mixup={cfg.mixup:g}, cutmix={cfg.cutmix:g}, mix_prob={cfg.mix_prob:g}, "
@@ -52,6 +52,7 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
         check_mix(cfg)
         check_rrc(cfg)
         check_clip(cfg)
+        check_layer_adapt(cfg)
     except ValueError as e:
         sys.stderr.write(f"{e}\n")
         return 2
@@ -70,6 +71,11 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
             what = "--optimizer lars" if cfg.optimizer == "lars" else "--lr-schedule poly"
             sys.stderr.write(f"{what} is not supported for --strategy ps: the parameter servers apply Adam at a "
                              "host-set rate (use the mirrored, multiworker or horovod script for large batches)\n")
+            return 2
+        if cfg.layer_adapt:
+            sys.stderr.write("--layer-adapt is not supported for --strategy ps: every parameter-server shard applies "
+                             "plain Adam to its slice of the buffer, so no process holds a whole layer to take the "
+                             "norms of (use the mirrored, multiworker or horovod script for large batches)\n")
             return 2
         if cfg.accum_steps != 1:
             sys.stderr.write("--accum-steps is not supported for --strategy ps: every worker push is one asynchronous "

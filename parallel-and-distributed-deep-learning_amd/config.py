@@ -47,6 +47,8 @@ class TrainConfig:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-7
+    layer_adapt: bool = False                      # additive: Adam with a per-layer trust ratio and decoupled
+                                                   # weight decay (LAMB); needs optimizer = adam
     lars_eta: float = 1e-3                         # LARS trust coefficient
     lars_eps: float = 0.0                          # LARS: added to the trust ratio's denominator
     label_smoothing: float = 0.0                   # eps of the loss target (1 - eps) * onehot + eps / num_classes
@@ -203,6 +205,14 @@ def check_clip(cfg: TrainConfig) -> None:
                          "gradient to take the global norm of")
 
 
+def check_layer_adapt(cfg: TrainConfig) -> None:
+    """--layer-adapt is Adam's per-layer form: with another optimizer it is a configuration error,
+    raised before anything is built."""
+    if cfg.layer_adapt and cfg.optimizer != "adam":
+        raise ValueError(f"--layer-adapt needs --optimizer adam (got --optimizer {cfg.optimizer}): it is Adam with a "
+                         "per-layer trust ratio; --optimizer lars is the momentum-SGD form")
+
+
 def make_config(preset: str = "single", **overrides) -> TrainConfig:
     if preset not in PRESETS:
         raise ValueError(f"unknown preset {preset!r}; choose from {sorted(PRESETS)}")
@@ -227,6 +237,10 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--momentum", type=float)
     a("--weight-decay", type=float, dest="weight_decay")
     a("--nesterov", action="store_true", default=None, help="SGD: Nesterov momentum")
+    a("--layer-adapt", action="store_true", default=None, dest="layer_adapt",
+      help="with --optimizer adam: LAMB, Adam whose step is scaled per layer by |w| / |update| with decoupled "
+           "--weight-decay (kernels only; biases and BN parameters take plain bias-corrected Adam); not with "
+           "--strategy ps")
     a("--lars-eta", type=float, dest="lars_eta", help="LARS trust coefficient")
     a("--lars-eps", type=float, dest="lars_eps", help="LARS: added to the trust ratio's denominator")
     a("--label-smoothing", type=float, dest="label_smoothing",

@@ -245,7 +245,7 @@ class Strategy:
                              nesterov=self.cfg.nesterov, weight_decay=self.cfg.weight_decay, beta1=self.cfg.beta1,
                              beta2=self.cfg.beta2, eps=self.cfg.adam_eps, lars_eta=self.cfg.lars_eta,
                              lars_eps=self.cfg.lars_eps, global_clipnorm=self.cfg.global_clipnorm,
-                             skip_nonfinite=self.cfg.skip_nonfinite)
+                             skip_nonfinite=self.cfg.skip_nonfinite, layer_adapt=self.cfg.layer_adapt)
         return eng, opt
 
     def _build(self, trainer):
@@ -699,7 +699,7 @@ class _LocalReplicas:
             opt = make_optimizer(cfg.optimizer, eng, lr=cfg.lr, momentum=cfg.momentum, nesterov=cfg.nesterov,
                                  weight_decay=cfg.weight_decay, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.adam_eps,
                                  lars_eta=cfg.lars_eta, lars_eps=cfg.lars_eps, global_clipnorm=cfg.global_clipnorm,
-                                 skip_nonfinite=cfg.skip_nonfinite)
+                                 skip_nonfinite=cfg.skip_nonfinite, layer_adapt=cfg.layer_adapt)
             self.replicas.append((eng, opt))
             self.augs.append(Augment(cfg, d, cfg.seed + 7919 * (global_rank_base + i)))
         self.comm = None

@@ -4,7 +4,8 @@ Adam reproduces TF/Keras `ResourceApplyAdam` (epsilon-hat form; imagenet-resnet5
 SGD reproduces `keras.optimizers.SGD(momentum, nesterov)` — the north-star optimizer
 (BASELINE.json).  LARS (You et al., the MLPerf ResNet-50 form) is the large-batch optimizer:
 momentum SGD whose step is scaled per layer by a trust ratio, in two launches over a segment
-table of the flat buffer.  On CPU the same update runs as torch ops (reference semantics).
+table of the flat buffer.  LAMB is Adam under the same per-layer rule, with decoupled weight decay
+(`make_optimizer("adam", ..., layer_adapt=True)`).  On CPU the same update runs as torch ops (reference semantics).
 """
 from __future__ import annotations
 
@@ -365,6 +366,72 @@ class LARS(FlatOptimizer):
         return {name: r[i] for i, (_, _, adapt, name) in enumerate(self.segments) if adapt}
 
 
+class LAMB(FlatOptimizer):
+    """Adam with a per-layer trust ratio and decoupled weight decay (You et al. 2019), reached as
+    `make_optimizer("adam", ..., layer_adapt=True)`.  For a kernel w with gradient g (gs the
+    gradient scale, t the step count):
+        m <- b1 m + (1 - b1) gs g;   v <- b2 v + (1 - b2) (gs g)^2
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + wd w
+        ratio = |w| / |u|   (1 when either norm is 0);   w <- w - lr ratio u
+    Biases and BN parameters take ratio 1 and no weight decay (the segments of `lars_segments`).
+    On the GPU the step is two launches over the LARS segment table, the norms in the same fixed
+    order (bit-identical on every replica and every run); lr, the step count and the trust
+    ratios stay on the device, so the step captures into a HIP graph."""
+
+    def __init__(self, engine, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, weight_decay=0.0, chunk=None):
+        super().__init__(engine, lr)
+        self.b1, self.b2, self.eps, self.wd = beta1, beta2, eps, weight_decay
+        self.m = torch.zeros_like(self.params)
+        self.v = torch.zeros_like(self.params)
+        self.chunk = int(chunk or LARS_CHUNK)
+        self.segments = lars_segments(engine.L)
+        self.table_host = lars_table([s[:3] for s in self.segments], self.chunk)
+        dev = self.params.device
+        self.ratios = torch.ones(len(self.segments), dtype=torch.float32, device=dev)
+        if self.on_gpu:
+            self.table = self.table_host.to(dev)
+            self.partials = torch.zeros(2 * lars_chunks(self.table_host, self.chunk), dtype=torch.float32, device=dev)
+
+    def step(self):
+        if self.on_gpu:
+            from ..ops.native import native
+            self._device_step(False)
+            self._iterations += 1
+            native.lamb(self.params, self.grads, self.m, self.v, self.table, self.table_host, self.chunk,
+                        self.partials, self.ratios, 0.0, 0.0, self.b1, self.b2, self.eps, self.wd, self.gscale,
+                        self.hs, self.gn)
+        else:
+            self._iterations += 1
+            skip, gs = self._host_clip()
+            if skip:
+                return
+            t = self._iterations
+            lr, c1, c2 = self.lr_at(t), 1 - self.b1 ** t, 1 - self.b2 ** t
+            for i, (off, size, adapt, _) in enumerate(self.segments):
+                w = self.params[off:off + size]
+                g = self.grads[off:off + size] * gs
+                m, v = self.m[off:off + size], self.v[off:off + size]
+                m.mul_(self.b1).add_(g, alpha=1 - self.b1)
+                v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+                u = (m / c1) / ((v / c2).sqrt() + self.eps)
+                ratio = 1.0
+                if adapt:
+                    u.add_(w, alpha=self.wd)
+                    wn, un = float((w * w).sum().sqrt()), float((u * u).sum().sqrt())
+                    if wn > 0 and un > 0:
+                        ratio = wn / un
+                self.ratios[i] = ratio
+                w.sub_(u, alpha=lr * ratio)
+
+    def state_tensors(self):
+        return {"m": self.m, "v": self.v}
+
+    def trust_ratios(self):
+        """{layer name: trust ratio of the most recent step} for the adapted (kernel) segments."""
+        r = self.ratios.detach().cpu().tolist()
+        return {name: r[i] for i, (_, _, adapt, name) in enumerate(self.segments) if adapt}
+
+
 def make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
     opt = _make_optimizer(name, engine, lr, **kw)
     if kw.get("global_clipnorm") is not None or kw.get("skip_nonfinite"):
@@ -373,6 +440,11 @@ def make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
 
 
 def _make_optimizer(name: str, engine, lr: float, **kw) -> FlatOptimizer:
+    if kw.get("layer_adapt"):
+        if name != "adam":
+            raise ValueError(f"layer_adapt is Adam's per-layer form: it needs optimizer 'adam' (got {name!r})")
+        return LAMB(engine, lr, kw.get("beta1", 0.9), kw.get("beta2", 0.999), kw.get("eps", 1e-7),
+                    kw.get("weight_decay", 0.0))
     if name == "lars":
         return LARS(engine, lr, kw.get("momentum", 0.9), kw.get("weight_decay", 0.0), kw.get("lars_eta", 1e-3),
                     kw.get("lars_eps", 0.0), kw.get("nesterov", False))
