@@ -643,31 +643,32 @@ void conv3x3c64_wgrad(Tensor x, Tensor g, Tensor dw) {
   p.N = (int)x.size(0); p.H = (int)x.size(1); p.W = (int)x.size(2);
   ok(pddl::conv3x3c64_wgrad_launch(p, cur_stream()), "conv3x3c64_wgrad");
 }
-// Fused 64-channel bottleneck boundary: out = relu(a . w3^T * scale3 + shift3 (+ res)), bits3;
-// y1 = relu(out . w1^T * scale1 + shift1), bits1 (a2: second K source of the fused projection).
+// Fused bottleneck boundary, F = 64 (stage 2) or 128 (stage 3) channels wide:
+// out = relu(a . w3^T * scale3 + shift3 (+ res)), bits3; y1 = relu(out . w1^T * scale1 + shift1), bits1.
 void c3c1(Tensor a, Tensor w3, Tensor scale3, Tensor shift3, OptT res, Tensor out, OptT bits3, Tensor w1,
           Tensor scale1, Tensor shift1, Tensor y1, OptT bits1) {
-  PCHECK(a.size(-1) == 64 && a.is_contiguous() && a.scalar_type() == torch::kBFloat16, "c3c1: a [..,64] bf16");
-  const int64_t M = a.numel() / 64;
-  PCHECK(M < (1LL << 30), "c3c1: too many rows");
-  PCHECK(w3.dim() == 2 && w3.size(0) == 256 && w3.size(1) == 64 && w3.is_contiguous(), "c3c1: w3 [256, 64]");
-  PCHECK(w1.dim() == 2 && w1.size(0) == 64 && w1.size(1) == 256 && w1.is_contiguous(), "c3c1: w1 [64, 256]");
-  PCHECK(scale3.numel() >= 256 && shift3.numel() >= 256 && scale1.numel() >= 64 && shift1.numel() >= 64,
+  const int64_t F = a.size(-1), C = 4 * F;
+  PCHECK((F == 64 || F == 128) && a.is_contiguous() && a.scalar_type() == torch::kBFloat16, "c3c1: a [..,64 | 128] bf16");
+  const int64_t M = a.numel() / F;
+  PCHECK(M < (1LL << 30) && M * C < (1LL << 31), "c3c1: too many rows");
+  PCHECK(w3.dim() == 2 && w3.size(0) == C && w3.size(1) == F && w3.is_contiguous(), "c3c1: w3 [4F, F]");
+  PCHECK(w1.dim() == 2 && w1.size(0) == F && w1.size(1) == C && w1.is_contiguous(), "c3c1: w1 [F, 4F]");
+  PCHECK(scale3.numel() >= C && shift3.numel() >= C && scale1.numel() >= F && shift1.numel() >= F,
          "c3c1: scale / shift sizes");
   for (const Tensor* t : {&scale3, &shift3, &scale1, &shift1})
     PCHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0, "c3c1: 16-byte aligned scale / shift");
-  PCHECK(out.numel() == M * 256 && out.is_contiguous() && out.scalar_type() == torch::kBFloat16, "c3c1: out [M,256]");
-  PCHECK(y1.numel() == M * 64 && y1.is_contiguous() && y1.scalar_type() == torch::kBFloat16, "c3c1: y1 [M,64]");
-  if (res.has_value()) PCHECK(res->numel() == M * 256 && res->is_contiguous(), "c3c1: res [M,256]");
-  if (bits3.has_value()) PCHECK(bits3->numel() == M * 32 && bits3->scalar_type() == torch::kUInt8, "c3c1: bits3 [M,32]");
-  if (bits1.has_value()) PCHECK(bits1->numel() == M * 8 && bits1->scalar_type() == torch::kUInt8, "c3c1: bits1 [M,8]");
+  PCHECK(out.numel() == M * C && out.is_contiguous() && out.scalar_type() == torch::kBFloat16, "c3c1: out [M,4F]");
+  PCHECK(y1.numel() == M * F && y1.is_contiguous() && y1.scalar_type() == torch::kBFloat16, "c3c1: y1 [M,F]");
+  if (res.has_value()) PCHECK(res->numel() == M * C && res->is_contiguous(), "c3c1: res [M,4F]");
+  if (bits3.has_value()) PCHECK(bits3->numel() == M * (C / 8) && bits3->scalar_type() == torch::kUInt8, "c3c1: bits3 [M,F/2]");
+  if (bits1.has_value()) PCHECK(bits1->numel() == M * (F / 8) && bits1->scalar_type() == torch::kUInt8, "c3c1: bits1 [M,F/8]");
   pddl::C3C1Params p{};
   p.a = bfp(a); p.w3 = bfp(w3);
   p.scale3 = f32p(scale3); p.shift3 = f32p(shift3); p.res = obfp(res); p.out = bfpm(out);
   p.bits3 = bits3.has_value() ? bits3->data_ptr<uint8_t>() : nullptr;
   p.w1 = bfp(w1); p.scale1 = f32p(scale1); p.shift1 = f32p(shift1); p.y1 = bfpm(y1);
   p.bits1 = bits1.has_value() ? bits1->data_ptr<uint8_t>() : nullptr;
-  p.M = (int)M;
+  p.M = (int)M; p.F = (int)F;
   ok(pddl::c3c1_launch(p, cur_stream()), "c3c1");
 }
 void maxpool_bwd(Tensor gy, Tensor idx, OptT xmask, Tensor gx, OptT colsum) {
@@ -1072,6 +1073,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     else if (which == "c64_grid") pddl::g_c64_grid = v;
     else if (which == "c64w_grid") pddl::g_c64w_grid = v;
     else if (which == "bwd1x1_grid") { TORCH_CHECK(v >= 0, "bwd1x1_grid: 0 (off) or a workgroup cap"); pddl::g_bwd1x1_grid = v; }
+    else if (which == "c3c1_grid") { TORCH_CHECK(v >= 0, "c3c1_grid: 0 (off) or a workgroup cap"); pddl::g_c3c1_grid = v; }
     else if (which == "bn_red_blocks") pddl::g_bn_red_blocks = v;
     else if (which == "bn_apply_blocks") pddl::g_bn_apply_blocks = v;
     else if (which == "pool_blocks") pddl::g_pool_blocks = v;

@@ -80,7 +80,7 @@ class HipEngine(SideStream):
     DEFER_OK = True         # segmented graphs may defer the side work into side graphs (_side_run)
     C64_OK = True           # stage-2 3x3 convs on the row-tile kernels (conv3x3c64.hip)
     C64_MIN_M = 262144      # ... from 4 x 256 CUs x 256-pixel tiles up (b >= 84 at 56 x 56)
-    C3C1_OK = True          # stage-2 boundaries: conv3 + next conv1 fused (c3c1.hip)
+    C3C1_OK = True          # stage-2 and stage-3 boundaries: conv3 + next conv1 fused (c3c1.hip)
     S2C_OK = True           # blocks feeding a downsampling block store only their stride-2 grid
     PROJ_BWD_OK = True      # conv2_block1: shortcut conv backward inside the fused conv3 backward
     PROJ_BWD_MIN_M = 200704 # ... from b64 at 56 x 56 up: b32 measured a wash (3.620 -> 3.629 ms against a 0.014
@@ -175,8 +175,9 @@ class HipEngine(SideStream):
         self.c64 = self.C64_OK and opt(E, "c64", True)
         self.c64w = self.c64 and opt(E, "c64w", True)
         self.c64_min_m = opt(E, "c64_min_m", self.C64_MIN_M)
-        # stage-2 block boundaries: conv3 + the next block's conv1 in one launch (c3c1.hip)
-        self.c3c1 = opt(E, "c3c1", 1) if self.C3C1_OK else 0
+        # block boundaries: conv3 + the next block's conv1 in one launch (c3c1.hip); 2: the plain
+        # stride-1 boundaries of stages 2 and 3, 1: stage 2 only, 0: off
+        self.c3c1 = opt(E, "c3c1", 2) if self.C3C1_OK else 0
         # stage-2 backward boundaries: the next block's conv1 data gradient computed inside this
         # block's fused conv3 backward (bwd1x1 pre form), its 256-channel result never re-read
         self.c1pre = self.C3C1_OK and opt(E, "c1pre", True)
@@ -546,12 +547,14 @@ class HipEngine(SideStream):
         return self.c64 and f == 64 and W + 2 <= 64 and M >= self.c64_min_m and bits
 
     def _c3c1_ok(self, b, nb) -> bool:
-        """Fuse block b's conv3 with block nb's conv1 (c3c1.hip): 64-channel stride-1 boundaries out of
-        a plain block (stage 2: conv2_block2 -> 3), not into a projection block.  (Out of the fused
-        projection block conv2_block1, K = 128, it measured no gain: 2.77 ms fused vs 1.87 + 0.90 ms
-        separate at b2560, profiles/r4_c3c1.txt.)"""
-        return (bool(self.c3c1) and nb is not None and b.filters == 64 and nb.filters == 64 and not b.proj
-                and not nb.proj and nb.stride == 1)
+        """Fuse block b's conv3 with block nb's conv1 (c3c1.hip): stride-1 boundaries out of a plain
+        block, not into a projection block -- 64 channels wide (stage 2: conv2_block2 -> 3) and, with
+        c3c1 >= 2, 128 channels wide (stage 3: conv3_block2 -> 3 and 3 -> 4; conv3_block4 feeds the
+        stride-2 grid).  (Out of a fused projection block, conv2_block1 with K = 128, it measured no
+        gain: 2.77 ms fused vs 1.87 + 0.90 ms separate at b2560, profiles/r4_c3c1.txt.)"""
+        wide = 128 if self.c3c1 >= 2 else 64
+        return (bool(self.c3c1) and nb is not None and b.filters == nb.filters and b.filters in (64, wide)
+                and not b.proj and not nb.proj and nb.stride == 1)
 
     def _c2_wgrad(self, y1, g2, c2n, f, B, Ho, g2_n):
         """Weight gradient of a bottleneck's stride-1 3x3 conv (on the side stream when two-stream)."""

@@ -31,13 +31,13 @@ def schedule(B, crop, fuse=True, fuse_bwd=True, fuse_bwd3=True, fuse_s2=True, fu
         ev.append(("maxpool_fwd", "pool", 0, B * (H1 * H1 + H2 * H2) * 64 * 2))
     H = H2
     geo = []
-    c3c1_on = opt(E, "c3c1", 1)
+    c3c1_on = opt(E, "c3c1", 2)
     s2c = opt(E, "s2c", True)
     blocks = list(L.blocks)
 
     def c3c1(b, nb):   # engine._c3c1_ok
-        return bool(c3c1_on) and nb is not None and b.filters == 64 and nb.filters == 64 and not b.proj \
-            and not nb.proj and nb.stride == 1
+        return bool(c3c1_on) and nb is not None and b.filters == nb.filters \
+            and b.filters in (64, 128 if c3c1_on >= 2 else 64) and not b.proj and not nb.proj and nb.stride == 1
     c1_done = False
     c64_min = opt(E, "c64_min_m", 262144)
     for bi, b in enumerate(blocks):
