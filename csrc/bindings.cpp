@@ -519,10 +519,14 @@ void stem_s2d(Tensor in, OptT flip, int64_t mode, int64_t Hc, int64_t Wc, int64_
   p.mix = mix_table(mix, p.B);
   if (rrc.has_value()) {   // a per-image box table (kernels.h): mode 3, whatever mode was passed
     PCHECK(rrc->is_cuda() && rrc->scalar_type() == torch::kInt32 && rrc->is_contiguous() && rrc->dim() == 2 &&
-           rrc->size(1) == 4 && rrc->size(0) >= p.B, "rrc: contiguous device int32 [>= B][4]");
+           (rrc->size(1) == 4 || rrc->size(1) == 16) && rrc->size(0) >= p.B,
+           "rrc: contiguous device int32 [>= B][4], or [>= B][16] with RandAugment rows");
     p.rrc = rrc->data_ptr<int32_t>();
     p.mode = 3;
     p.antialias = antialias ? 1 : 0;   // (ignored without a box table)
+    p.aug = rrc->size(1) == 16;
+    // the grey means of the rows with a contrast op, into column 15 of the table itself
+    if (p.aug) ok(pddl::stem_gray_mean_launch(p, rrc->data_ptr<int32_t>(), cur_stream()), "stem_gray_mean");
   }
   p.scale = 1.f / 255.f;
   p.Hs = (int)((Hc + 6) / 2); p.Ws = (int)((Wc + 6) / 2);
@@ -1004,10 +1008,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_s2d", &stem_s2d, REL, py::arg("images"), py::arg("flip"), py::arg("mode"), py::arg("Hc"), py::arg("Wc"),
         py::arg("oy"), py::arg("ox"), py::arg("out"), py::arg("crop_dev"), py::arg("mix") = py::none(),
         py::arg("rrc") = py::none(), py::arg("antialias") = false);
-  // (kernel tests) what the last stem_s2d launch ran: ("pixel" | "rows" | "band" | "aa_band" | "aa_pixel",
-  // s2d rows per band workgroup)
+  // (kernel tests) what the last stem_s2d launch ran: ("pixel" | "rows" | "band" | "aa_band" | "aa_pixel" |
+  // "aug_tile" | "aug_pixel", s2d rows per band workgroup)
   m.def("stem_last_launch", []() {
-    static const char* const form[] = {"pixel", "rows", "band", "aa_band", "aa_pixel"};
+    static const char* const form[] = {"pixel", "rows", "band", "aa_band", "aa_pixel", "aug_tile", "aug_pixel"};
     int f = 0, band = 0;
     pddl::stem_last_launch(&f, &band);
     return py::make_tuple(form[f], band);

@@ -204,6 +204,7 @@ struct StemParams {
   const int32_t* mix;                 // optional mixup / CutMix table [B][8] (below); null: no mixing
   const int32_t* rrc;                 // mode 3: the random-resized-crop box table [B][4] (below)
   int antialias;                      // mode 3: a box side that is shrunk takes a triangle filter (below)
+  int aug;                            // mode 3: the table is [B][16], boxes plus RandAugment rows (below)
 };
 // The per-image box table of mode 3, int32 [B][4], row b = {y0, x0, h, w}: a box of the Hin x Win
 // source in whole pixels that becomes image b's Hc x Wc picture (crop, then bilinear resize with
@@ -229,6 +230,30 @@ struct StemParams {
 // acc = fma(float(u_k), h_k, acc), v = fdiv_rn(acc, float(D_y)) * scale.  With one axis shrunk the
 // other keeps its lerp: h = fma(b - a, fx, a), or v = fma(bot - top, fy, top) * scale.  The launcher
 // returns an error string when S or the weight arithmetic could overflow int32 for the source.
+// RandAugment rows (`aug`; uint8 input, no antialias; stem_aug.hip).  The table is int32 [B][16]: columns
+// 0..3 are the box as above, and row b goes on with
+//   4..9   a b c / d e f: the inverse affine map, Q16 fixed point
+//   10     bits 4k..4k+3: colour op k of the chain (k = 0..3; 0 none, 1 brightness, 2 color,
+//          3 contrast, 4 solarize, 5 posterize; other codes do nothing); bit 16: has_geo
+//   11..14 the fp32 parameter (bits) of op k
+//   15     the box's grey mean (fp32 bits), written by stem_gray_mean before the stem kernel reads it
+// Geometry.  A row with has_geo = 0 takes the box arithmetic above (rrc_tap), bit for bit.  With has_geo,
+// picture pixel (x, y) has u = 2x + 1 - Wc, v = 2y + 1 - Hc and, in int64,
+//   U = a u + b v + c (negated for a flipped image: the flip comes before the warp),  V = d u + e v + f:
+// doubled centre-relative picture coordinates in Q16 (the identity is a = e = 65536; a shift by t
+// pixels is c = 2 t 65536).  |U| >= Wc 2^16 or |V| >= Hc 2^16 is fill: raw value 128 in every channel.
+// Otherwise X8 = floor((U + Wc 2^16) w / (Wc 2^9)) - 128 is the position in the box in Q8: the taps
+// are box columns clamp(X8 >> 8, 0, w-1) and clamp((X8 >> 8) + 1, 0, w-1), the weight fx = (X8 & 255) / 256
+// (exact in fp32); rows likewise from V, h and Hc; then the lerps above, horizontal first.  All
+// geometric ops of an image are one matrix, sampled once from the source.
+// Colour chain, on the raw 0..255 fp32 triple (r, g, b) after the lerps (fill pixels too), before
+// `* scale` and the mixing; every op ends with min(max(., 0), 255):
+//   brightness k: k v                      solarize thr: v >= thr ? 255 - v : v
+//   color k:      fma(k, v - G, G) with G = fma(0.114, b, fma(0.587, g, 0.299 r))
+//   contrast k:   fma(k, v - m, m), m = col 15    posterize mask: float(int(v) & int(mask))
+// stem_gray_mean (one workgroup per image; a row without a contrast op is left alone): S = the sum over the
+// clamped box of the integer luma (19595 R + 38470 G + 7471 B + 32768) >> 16 of the source pixels (exact),
+// m = fdiv_rn(float(S), float(h w)).  The mix table's partner takes its own row: box, map, chain and mean.
 // The per-image mix table, int32 [B][8], shared by the stem kernels and the training heads.  Row b:
 //   0      partner: index in this batch of the image mixed into image b
 //   1..4   y0, x0, y1, x1: half-open box in the Hc x Wc preprocessed image (after each image's own
@@ -248,9 +273,15 @@ const char* stem_rrc_launch(const StemParams& p, void* out, int out_f32, hipStre
 // Mode 3 with `antialias` (stem_aa.hip; stem_rrc_launch forwards to it): likewise a band form and a
 // per-pixel form.
 const char* stem_aa_launch(const StemParams& p, void* out, int out_f32, hipStream_t s);
+// Mode 3 with `aug` (stem_aug.hip; stem_rrc_launch forwards to it): the tile form (a 16 x 16 block of s2d
+// pixels per workgroup, the bounding rectangle of its taps staged in LDS when it fits; g_stem_variant == 2)
+// and a per-pixel form (the default: the faster one as measured, profiles/randaug_stem.txt).
+const char* stem_aug_launch(const StemParams& p, void* out, int out_f32, hipStream_t s);
+// Column 15 of every row of `table` (p.rrc, [B][16]) that has a contrast op; launched before the stem kernel.
+const char* stem_gray_mean_launch(const StemParams& p, int32_t* table, hipStream_t s);
 // What the calling thread's last stem_s2d launch ran (tests): form 0 per-pixel, 1 row form, 2 band
-// form, 3 antialias band form, 4 antialias per-pixel form, and a band form's s2d rows per
-// workgroup; kept per thread, since replicas launch from several.
+// form, 3 antialias band form, 4 antialias per-pixel form, 5 RandAugment tile form, 6 RandAugment
+// per-pixel form, and a band form's s2d rows per workgroup; kept per thread, since replicas launch from several.
 void stem_note_launch(int form, int band);
 void stem_last_launch(int* form, int* band);
 extern int g_stem_rrc_band;   // tuning knob like g_stem_variant: > 0 caps the band height

@@ -261,6 +261,7 @@ static const char* stem_rrc_go(const StemParams& p, OutT* out, hipStream_t s) {
 }
 
 const char* stem_rrc_launch(const StemParams& p, void* out, int out_f32, hipStream_t s) {
+  if (p.aug) return stem_aug_launch(p, out, out_f32, s);        // [B][16] RandAugment rows: stem_aug.hip
   if (p.antialias) return stem_aa_launch(p, out, out_f32, s);   // triangle-filter forms: stem_aa.hip
   return out_f32 ? stem_rrc_go<float>(p, reinterpret_cast<float*>(out), s)
                  : stem_rrc_go<uint16_t>(p, reinterpret_cast<uint16_t*>(out), s);

@@ -11,7 +11,8 @@ import os
 import sys
 from typing import List, Optional
 
-from .config import check_accum, check_clip, check_layer_adapt, check_loss, check_mix, check_rrc, config_from_args
+from .config import (check_accum, check_clip, check_layer_adapt, check_loss, check_mix, check_randaug, check_rrc,
+                     config_from_args)
 
 
 def _banner(cfg, strategy):
@@ -25,7 +26,8 @@ def _banner(cfg, strategy):
           f"skip_nonfinite={cfg.skip_nonfinite}, "
           f"mixup={cfg.mixup:g}, cutmix={cfg.cutmix:g}, mix_prob={cfg.mix_prob:g}, "
           f"rrc={cfg.rrc}, rrc_scale={cfg.rrc_scale[0]:g}-{cfg.rrc_scale[1]:g}, "
-          f"rrc_ratio={cfg.rrc_ratio[0]:g}-{cfg.rrc_ratio[1]:g}, antialias={cfg.antialias}", flush=True)
+          f"rrc_ratio={cfg.rrc_ratio[0]:g}-{cfg.rrc_ratio[1]:g}, antialias={cfg.antialias}, "
+          f"randaugment={tuple(cfg.randaugment) if cfg.randaugment else None}", flush=True)
 
 
 def model_summary(cfg) -> str:
@@ -51,6 +53,7 @@ def run(preset: str, argv: Optional[List[str]] = None, extra=None) -> int:
         check_loss(cfg)
         check_mix(cfg)
         check_rrc(cfg)
+        check_randaug(cfg)
         check_clip(cfg)
         check_layer_adapt(cfg)
     except ValueError as e:

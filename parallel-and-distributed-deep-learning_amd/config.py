@@ -63,6 +63,8 @@ class TrainConfig:
     rrc_ratio: Tuple[float, float] = (3 / 4, 4 / 3)   # its aspect ratio w / h, log-uniform
     antialias: bool = False                        # additive: a box side that is shrunk is resampled with a triangle
                                                    # filter (--rrc boxes, and the evaluation resize at image_size > crop)
+    randaugment: Optional[Tuple[int, int]] = None  # additive: RandAugment (N ops per image at magnitude M of 30), one
+                                                   # affine warp and a colour chain inside the preprocess kernel
     global_clipnorm: Optional[float] = None        # additive (Keras `global_clipnorm`): the whole gradient is scaled
                                                    # by C / max(|g|, C) before the update; None = off
     skip_nonfinite: bool = False                   # additive: a step whose gradient norm is inf / nan updates nothing
@@ -193,6 +195,20 @@ def check_rrc(cfg: TrainConfig) -> None:
                              f"(got {tuple(r)!r})")
 
 
+def check_randaug(cfg: TrainConfig) -> None:
+    """--randaugment N M: N outside 1..4 (the kernel's colour chain holds four ops), M outside 0..30, or
+    --antialias with it, is a configuration error, raised before anything is built."""
+    ra = getattr(cfg, "randaugment", None)
+    if ra is None:
+        return
+    ok = len(ra) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in ra)
+    if not ok or not 1 <= ra[0] <= 4 or not 0 <= ra[1] <= 30:
+        raise ValueError(f"--randaugment must be N M with integers 1 <= N <= 4 and 0 <= M <= 30 (got {tuple(ra)!r})")
+    if cfg.antialias:
+        raise ValueError("--randaugment cannot be combined with --antialias: the affine warp samples the source "
+                         "with two bilinear taps per axis (drop one of the two)")
+
+
 def check_clip(cfg: TrainConfig) -> None:
     """--global-clipnorm C / --skip-nonfinite: a threshold that is no finite number > 0, or either
     option on the parameter server, is a configuration error, raised before anything is built."""
@@ -268,6 +284,11 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
       help="the box's area as a fraction of the image, uniform in [LO, HI] (default 0.08 1.0)")
     a("--rrc-ratio", type=float, nargs=2, dest="rrc_ratio", metavar=("LO", "HI"),
       help="the box's aspect ratio w / h, log-uniform in [LO, HI] (default 0.75 1.3333)")
+    a("--randaugment", type=int, nargs=2, metavar=("N", "M"),
+      help="RandAugment inside the preprocess kernel: per training image N (1-4) ops drawn from identity, shear-x/y, "
+           "translate-x/y, rotate, brightness, color, contrast, posterize, solarize at magnitude M (0-30, the "
+           "torchvision tables); the geometric ops are composed into one affine map and the source is sampled once; "
+           "not with --antialias")
     a("--global-clipnorm", type=float, dest="global_clipnorm",
       help="C > 0: scale the whole gradient by C / max(|g|, C) before the update (Keras global_clipnorm), the norm "
            "taken on the device in a fixed order; with --accum-steps K the optimizer only runs on the K-th "

@@ -91,6 +91,71 @@ def rrc_resample(images: torch.Tensor, rrc: torch.Tensor, Hc: int, Wc: int, flip
     return ((top + (bot - top) * fy) * (1.0 / 255.0)).permute(0, 3, 1, 2)
 
 
+def aug_resample(images: torch.Tensor, table: torch.Tensor, Hc: int, Wc: int, flip: Optional[torch.Tensor] = None):
+    """rrc_resample for a [B][16] table with RandAugment rows (kernels.h, `StemParams::rrc`): a row with
+    has_geo samples its box through the Q16 inverse affine map (all decisions and tap indices in
+    integers, the weights multiples of 1/256; outside the picture is fill, raw 128), a row without
+    takes rrc_resample's taps; then the row's colour chain on the raw values.  uint8 images."""
+    B, H, W, _ = images.shape
+    dev = images.device
+    t = table[:B].to(dev).long()
+    y0, x0 = t[:, 0].clamp(0, H - 1), t[:, 1].clamp(0, W - 1)
+    h, w = torch.minimum(t[:, 2].clamp_min(1), H - y0), torch.minimum(t[:, 3].clamp_min(1), W - x0)
+    fl = flip.to(dev).bool() if flip is not None else torch.zeros(B, dtype=torch.bool, device=dev)
+    ys = torch.arange(Hc, device=dev).expand(B, Hc)
+    xs = torch.arange(Wc, device=dev).expand(B, Wc)
+    ya, yb, fy = (v.view(B, Hc, 1).expand(B, Hc, Wc) for v in rrc_taps(ys, h, Hc))
+    xa, xb, fx = (v.view(B, 1, Wc).expand(B, Hc, Wc) for v in rrc_taps(torch.where(fl.view(B, 1), Wc - 1 - xs, xs), w, Wc))
+    # the affine rows
+    geo = ((t[:, 10] >> 16) & 1).bool().view(B, 1, 1)
+    u, v = (2 * xs + 1 - Wc).view(B, 1, Wc), (2 * ys + 1 - Hc).view(B, Hc, 1)
+    m = t[:, 4:10].view(B, 6, 1, 1)
+    U, V = m[:, 0] * u + m[:, 1] * v + m[:, 2], m[:, 3] * u + m[:, 4] * v + m[:, 5]
+    U = torch.where(fl.view(B, 1, 1), -U, U)
+    fill = geo & ((U.abs() >= (Wc << 16)) | (V.abs() >= (Hc << 16)))
+
+    def q8(P, n, N):     # (clamped first: a fill position takes no taps)
+        P = P.clamp(1 - (N << 16), (N << 16) - 1)
+        X8 = torch.div((P + (N << 16)) * n.view(B, 1, 1), N << 9, rounding_mode="floor") - 128
+        k, hi = X8 >> 8, n.view(B, 1, 1) - 1
+        return torch.minimum(k.clamp_min(0), hi), torch.minimum((k + 1).clamp_min(0), hi), (X8 & 255).float() / 256.0
+    gya, gyb, gfy = q8(V, h, Hc)
+    gxa, gxb, gfx = q8(U, w, Wc)
+    ya, yb, fy = torch.where(geo, gya, ya), torch.where(geo, gyb, yb), torch.where(geo, gfy, fy).unsqueeze(-1)
+    xa, xb, fx = torch.where(geo, gxa, xa), torch.where(geo, gxb, xb), torch.where(geo, gfx, fx).unsqueeze(-1)
+    img = images.float()
+    bi = torch.arange(B, device=dev).view(B, 1, 1)
+
+    def tap(yy, xx):
+        return img[bi, y0.view(B, 1, 1) + yy, x0.view(B, 1, 1) + xx]                      # [B,Hc,Wc,3]
+    top = tap(ya, xa) + (tap(ya, xb) - tap(ya, xa)) * fx
+    bot = tap(yb, xa) + (tap(yb, xb) - tap(yb, xa)) * fx
+    raw = torch.where(fill.unsqueeze(-1), torch.full((), 128.0, device=dev), top + (bot - top) * fy)
+    # the colour chains
+    par = t[:, 11:15].to(torch.int32).contiguous().view(torch.float32)
+    out = []
+    for b in range(B):
+        x = raw[b]
+        for k in range(4):
+            op, a = int(t[b, 10] >> (4 * k)) & 15, par[b, k]
+            if op == 1:
+                x = (a * x).clamp(0, 255)
+            elif op == 2:
+                g = (0.299 * x[..., 0] + 0.587 * x[..., 1] + 0.114 * x[..., 2]).unsqueeze(-1)
+                x = (g + a * (x - g)).clamp(0, 255)
+            elif op == 3:
+                box = images[b, int(y0[b]):int(y0[b] + h[b]), int(x0[b]):int(x0[b] + w[b])].long()
+                luma = (19595 * box[..., 0] + 38470 * box[..., 1] + 7471 * box[..., 2] + 32768) >> 16
+                g = luma.sum().float() / float(h[b] * w[b])
+                x = (g + a * (x - g)).clamp(0, 255)
+            elif op == 4:
+                x = torch.where(x >= a, 255.0 - x, x)
+            elif op == 5:
+                x = (x.int() & int(a)).float()
+        out.append(x)
+    return (torch.stack(out) * (1.0 / 255.0)).permute(0, 3, 1, 2)
+
+
 def aa_weights(o: torch.Tensor, n: torch.Tensor, N: int, size: int) -> torch.Tensor:
     """The triangle-filter weights of the antialias definition (kernels.h, `StemParams::antialias`),
     int64 [B][N][size]: u_i = 2n - |(2i+1) N - (2o+1) n| of box pixel i for output index o [B][N] along
@@ -150,7 +215,8 @@ def preprocess(images: torch.Tensor, crop: int, training: bool, flip: Optional[t
     only): a random-resized-crop box table, which replaces the crop / resize.  antialias: box tables
     are resampled with the triangle filter, and so is the evaluation resize of a larger source."""
     if training and rrc is not None:
-        x = (aa_resample if antialias else rrc_resample)(images, rrc, crop, crop, flip)
+        wide = rrc.shape[1] == 16                # (RandAugment rows; --antialias is rejected with them)
+        x = (aug_resample if wide else aa_resample if antialias else rrc_resample)(images, rrc, crop, crop, flip)
         return mix_pixels(x, mix) if mix is not None else x
     if not training and antialias and crop < images.shape[1]:
         from ..train.rrc import full_table

@@ -826,9 +826,10 @@ def run_ps_job(cfg, num_ps: Optional[int] = None, num_workers: Optional[int] = N
     """Entry of imagenet-resnet50-ps.py.  Under torchrun (WORLD_SIZE = P + W) every process
     takes its role from RANK; otherwise spawn the whole cluster locally (the reference's
     create_in_process_cluster, imagenet-resnet50-ps.py:31-65)."""
-    from ..config import check_accum, check_clip, check_loss, check_mix, check_rrc
+    from ..config import check_accum, check_clip, check_loss, check_mix, check_randaug, check_rrc
     check_rrc(cfg)
-    check_mix(cfg)                                # (--mixup / --cutmix: every worker mixes its own batches)
+    check_randaug(cfg)
+    check_mix(cfg)                              # (--mixup / --cutmix: every worker mixes its own batches)
     check_accum(cfg)                              # (--accum-steps > 1: every push is one asynchronous update)
     check_clip(cfg)                               # (no process here holds a whole gradient to take the norm of)
     check_loss(cfg)                               # (--label-smoothing: every worker's own loss head takes it)
@@ -925,7 +926,7 @@ class ParameterServerStrategy:
             from ..train.graph import GraphedTrainStep   # forward + backward as one HIP graph
             self.graphed = GraphedTrainStep(eng, None, cfg.batch_size, (cfg.image_size, cfg.image_size),
                                             1.0 / cfg.batch_size, with_optimizer=False, mix=self.aug.mixing,
-                                            rrc=self.aug.boxes.enabled)
+                                            rrc=self.aug.table_cols)
         self.acc = torch.zeros(2, dtype=torch.float64, device=cl.device)
         self.n_img = 0
 

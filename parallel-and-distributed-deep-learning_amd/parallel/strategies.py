@@ -28,6 +28,7 @@ from ..data.datasets import Pipeline, make_source
 from ..models.resnet50 import ParamLayout
 from ..train.mix import MixSampler, identity_table
 from ..train.optim import make_optimizer
+from ..train import randaug
 from ..train.rrc import RrcSampler
 from ..utils import profiling as prof
 from ..utils.envopts import opt
@@ -118,6 +119,8 @@ class Augment:
                                   getattr(cfg, "mix_prob", 1.0), cfg.crop, cfg.crop, seed)
         self.boxes = RrcSampler(getattr(cfg, "rrc", False), getattr(cfg, "rrc_scale", (0.08, 1.0)),
                                 getattr(cfg, "rrc_ratio", (3 / 4, 4 / 3)), cfg.image_size, cfg.image_size, seed)
+        self.randaug = randaug.RandAugSampler(getattr(cfg, "randaugment", None), cfg.crop, seed)
+        self._off = (0, 0)     # the crop offset of the last __call__ (the boxes of --randaugment without --rrc)
         self._stages = {}      # table kind -> [[pinned host table, event of its last upload]], used in turn
         self._turns = {}
 
@@ -141,12 +144,23 @@ class Augment:
             t = identity_table(B)
         return self._upload("mix", t)
 
+    @property
+    def table_cols(self) -> int:
+        """The width of the per-image table the stem reads (the `rrc=` flag of the graph builders):
+        0 none, 4 boxes (--rrc), 16 boxes and RandAugment rows (--randaugment)."""
+        return randaug.COLS if self.randaug.enabled else 4 if self.boxes.enabled else 0
+
     def rrc(self, B):
         """The device table [B][4] of this batch's random-resized-crop boxes (one draw per image),
-        uploaded like the mix table; None without --rrc."""
-        if not self.boxes.enabled:
+        uploaded like the mix table; None without --rrc.  With --randaugment the table is [B][16]
+        (train/randaug.py): the boxes, or without --rrc the crop window this batch drew, and each
+        image's affine map and colour chain."""
+        if not self.table_cols:
             return None
-        return self._upload("rrc", self.boxes.draw(B))
+        if not self.randaug.enabled:
+            return self._upload("rrc", self.boxes.draw(B))
+        boxes = self.boxes.draw(B) if self.boxes.enabled else randaug.crop_boxes(B, self._off, self.cfg.crop)
+        return self._upload("rrc", self.randaug.draw(boxes))
 
     def _upload(self, kind, t):
         B, cols = t.shape
@@ -176,6 +190,7 @@ class Augment:
         if self.cfg.crop < self.cfg.image_size and not self.boxes.enabled:   # (--rrc: each image has its own box)
             m = self.cfg.image_size - self.cfg.crop
             off = (int(self.rng.integers(0, m + 1)), int(self.rng.integers(0, m + 1)))
+        self._off = off
         return flip, off
 
 
@@ -183,11 +198,12 @@ class Strategy:
     name = "base"
 
     def __init__(self, cfg):
-        from ..config import check_accum, check_clip, check_loss, check_mix, check_rrc
+        from ..config import check_accum, check_clip, check_loss, check_mix, check_randaug, check_rrc
         check_accum(cfg)
         check_loss(cfg)
         check_mix(cfg)
         check_rrc(cfg)
+        check_randaug(cfg)
         check_clip(cfg)
         self.cfg = cfg
         self.accum = None            # train/accum.py GradAccumulator with --accum-steps K > 1
@@ -346,7 +362,7 @@ class SingleStrategy(Strategy):
             from ..train.graph import GraphedTrainStep   # HIP-graph replay of the whole step
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.boxes.enabled)
+                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.table_cols)
 
     def train_step(self, images, labels):
         self._fault_tick()
@@ -430,7 +446,7 @@ class HorovodStrategy(_ProcessGroupMixin, Strategy):
             from ..train.graph import GraphedTrainStep   # one rank: the whole step as one HIP graph
             B = self.cfg.batch_size
             self.graphed = GraphedTrainStep(self.engine, self.opt, B, (self.cfg.image_size, self.cfg.image_size),
-                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.boxes.enabled)
+                                            1.0 / B, mix=self.aug.mixing, rrc=self.aug.table_cols)
         # bucket_mb <= 0: autotune (Horovod's HOROVOD_AUTOTUNE analogue for the fusion threshold)
         self._tune = None
         mb = self.cfg.bucket_mb
@@ -850,7 +866,7 @@ class _LocalReplicas:
             with torch.cuda.device(d):
                 g = SegmentedStepGraphs(eng, optim, B, (H, W), 1.0 / global_batch, self.buckets,
                                         image_dtype=parts[0][0].dtype, mix=self.augs[len(self.graphs)].mixing,
-                                        rrc=self.augs[len(self.graphs)].boxes.enabled)
+                                        rrc=self.augs[len(self.graphs)].table_cols)
                 g.capture()
                 self.graphs.append(g)
         self.comm_streams = [torch.cuda.Stream(device=d) for d in self.devices]
@@ -1185,7 +1201,7 @@ class _LocalReplicas:
         g = getattr(self, "_whole", None)
         if g is None or g.B != B or g.gscale != 1.0 / global_batch or tuple(g.images.shape[1:3]) != tuple(im.shape[1:3]):
             g = self._whole = GraphedTrainStep(eng, opt, B, tuple(im.shape[1:3]), 1.0 / global_batch,
-                                               image_dtype=im.dtype, mix=self.augs[0].mixing, rrc=self.augs[0].boxes.enabled)
+                                               image_dtype=im.dtype, mix=self.augs[0].mixing, rrc=self.augs[0].table_cols)
         with torch.cuda.device(d):
             flip, off = self.augs[0](B)
             return g(im, lb, flip, off, self.augs[0].mix(B, graphed=True), self.augs[0].rrc(B)).clone()

@@ -26,6 +26,7 @@ from typing import Optional, Tuple
 import torch
 
 from .mix import identity_table
+from . import randaug
 from .rrc import full_table
 
 
@@ -95,8 +96,11 @@ class GraphedTrainStep:
         self.mix = torch.from_numpy(identity_table(batch)).to(dev) if mix else None
         self._mix_identity = True     # (mix holds the identity table: a table-less load needs no copy)
         # rrc=True (a job with --rrc): the step is captured with the static box table (whole-image boxes
-        # until the first load; every load of such a step brings its batch's table)
+        # until the first load; every load of such a step brings its batch's table); rrc=16 (--randaugment):
+        # the table is the widened one of train/randaug.py, identity rows until the first load
         self.rrc = torch.from_numpy(full_table(batch, *image_hw)).to(dev) if rrc else None
+        if rrc == randaug.COLS:
+            self.rrc = torch.from_numpy(randaug.widen(full_table(batch, *image_hw))).to(dev)
         self._flip_zero = True        # (flip holds zeros: a flip-less load needs no memset)
         self._crop_host = (0, 0)      # (the tuple crop currently in `crop`: unchanged -> no copy)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
