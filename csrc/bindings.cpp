@@ -650,12 +650,18 @@ void conv3x3c64_wgrad(Tensor x, Tensor g, Tensor dw) {
 // Fused bottleneck boundary, F = 64 (stage 2) or 128 (stage 3) channels wide:
 // out = relu(a . w3^T * scale3 + shift3 (+ res)), bits3; y1 = relu(out . w1^T * scale1 + shift1), bits1.
 void c3c1(Tensor a, Tensor w3, Tensor scale3, Tensor shift3, OptT res, Tensor out, OptT bits3, Tensor w1,
-          Tensor scale1, Tensor shift1, Tensor y1, OptT bits1) {
+          Tensor scale1, Tensor shift1, Tensor y1, OptT bits1, OptT a2) {
   const int64_t F = a.size(-1), C = 4 * F;
   PCHECK((F == 64 || F == 128) && a.is_contiguous() && a.scalar_type() == torch::kBFloat16, "c3c1: a [..,64 | 128] bf16");
   const int64_t M = a.numel() / F;
   PCHECK(M < (1LL << 30) && M * C < (1LL << 31), "c3c1: too many rows");
-  PCHECK(w3.dim() == 2 && w3.size(0) == C && w3.size(1) == F && w3.is_contiguous(), "c3c1: w3 [4F, F]");
+  // a2: the dual-source form (conv2_block1: [a | a2] . w3^T with the fused projection weight)
+  if (a2.has_value()) {
+    PCHECK(F == 64 && !res.has_value(), "c3c1: a2 needs F = 64 and no res");
+    PCHECK(a2->numel() == M * 64 && a2->is_contiguous() && a2->scalar_type() == torch::kBFloat16, "c3c1: a2 [M,64] bf16");
+  }
+  const int64_t K3 = a2.has_value() ? F + 64 : F;
+  PCHECK(w3.dim() == 2 && w3.size(0) == C && w3.size(1) == K3 && w3.is_contiguous(), "c3c1: w3 [4F, F] (a2: [4F, F + 64])");
   PCHECK(w1.dim() == 2 && w1.size(0) == F && w1.size(1) == C && w1.is_contiguous(), "c3c1: w1 [F, 4F]");
   PCHECK(scale3.numel() >= C && shift3.numel() >= C && scale1.numel() >= F && shift1.numel() >= F,
          "c3c1: scale / shift sizes");
@@ -672,7 +678,7 @@ void c3c1(Tensor a, Tensor w3, Tensor scale3, Tensor shift3, OptT res, Tensor ou
   p.bits3 = bits3.has_value() ? bits3->data_ptr<uint8_t>() : nullptr;
   p.w1 = bfp(w1); p.scale1 = f32p(scale1); p.shift1 = f32p(shift1); p.y1 = bfpm(y1);
   p.bits1 = bits1.has_value() ? bits1->data_ptr<uint8_t>() : nullptr;
-  p.M = (int)M; p.F = (int)F;
+  p.M = (int)M; p.F = (int)F; p.a2 = obfp(a2);
   ok(pddl::c3c1_launch(p, cur_stream()), "c3c1");
 }
 void maxpool_bwd(Tensor gy, Tensor idx, OptT xmask, Tensor gx, OptT colsum) {
@@ -1031,7 +1037,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3c64_wgrad", &conv3x3c64_wgrad, REL, py::arg("x"), py::arg("g"), py::arg("dw"));
   m.def("c3c1", &c3c1, REL, py::arg("a"), py::arg("w3"), py::arg("scale3"), py::arg("shift3"),
         py::arg("res"), py::arg("out"), py::arg("bits3"), py::arg("w1"), py::arg("scale1"), py::arg("shift1"),
-        py::arg("y1"), py::arg("bits1"));
+        py::arg("y1"), py::arg("bits1"), py::arg("a2") = py::none());
   m.def("conv3x3c64_partial_rows", [](int64_t M) { return pddl::conv3x3c64_partial_rows((int)M); });
   m.def("gap_fwd", &gap_fwd, REL);
   m.def("gap_bwd", &gap_bwd, REL);

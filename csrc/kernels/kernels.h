@@ -351,9 +351,10 @@ struct C3C1Params {
   uint16_t* y1;                // [M][F] block b+1 conv1 output
   uint8_t* bits1;              // optional [M][F/8]
   int M, F;
+  const uint16_t* a2;          // optional [M][64] second K source (F = 64, no res): w3 is then [256][64 + 64]
 };
 const char* c3c1_launch(const C3C1Params& p, hipStream_t s);
-extern int g_c3c1_grid;                // test cap on the 128-channel form's workgroup count, 0 off
+extern int g_c3c1_grid;                // test cap on the persistent kernels' workgroup count (128 wide; 64 wide with a2), 0 off
 const char* stem_pool_bwd_launch(StemPoolBwdParams p, hipStream_t s);
 int stem_pool_bwd_partial_rows(int B, int H2, int PB);
 int stem_pool_lds_bytes(int Ws, int W1);

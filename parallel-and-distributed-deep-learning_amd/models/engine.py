@@ -81,6 +81,7 @@ class HipEngine(SideStream):
     C64_OK = True           # stage-2 3x3 convs on the row-tile kernels (conv3x3c64.hip)
     C64_MIN_M = 262144      # ... from 4 x 256 CUs x 256-pixel tiles up (b >= 84 at 56 x 56)
     C3C1_OK = True          # stage-2 and stage-3 boundaries: conv3 + next conv1 fused (c3c1.hip)
+    C3C1_PROJ_MIN_M = 16384 # conv2_block1 -> 2 fused from one 64-row tile per CU of a 256-CU persistent grid up
     S2C_OK = True           # blocks feeding a downsampling block store only their stride-2 grid
     PROJ_BWD_OK = True      # conv2_block1: shortcut conv backward inside the fused conv3 backward
     PROJ_BWD_MIN_M = 200704 # ... from b64 at 56 x 56 up: b32 measured a wash (3.620 -> 3.629 ms against a 0.014
@@ -178,6 +179,11 @@ class HipEngine(SideStream):
         # block boundaries: conv3 + the next block's conv1 in one launch (c3c1.hip); 2: the plain
         # stride-1 boundaries of stages 2 and 3, 1: stage 2 only, 0: off
         self.c3c1 = opt(E, "c3c1", 2) if self.C3C1_OK else 0
+        # conv2_block1 -> 2 (out of the stage-2 projection block): its dual-source conv3 + shortcut
+        # GEMM and conv2_block2's conv1 in one launch (the c3c1 dual form), from the batch at which
+        # every CU of the persistent grid gets a tile
+        self.c3c1_proj = bool(self.c3c1) and self.fuse_proj and opt(E, "c3c1_proj", True)
+        self.c3c1_proj_min_m = opt(E, "c3c1_proj_min_m", self.C3C1_PROJ_MIN_M)
         # stage-2 backward boundaries: the next block's conv1 data gradient computed inside this
         # block's fused conv3 backward (bwd1x1 pre form), its 256-channel result never re-read
         self.c1pre = self.C3C1_OK and opt(E, "c1pre", True)
@@ -546,15 +552,19 @@ class HipEngine(SideStream):
     def _use_c64(self, f, M, W, bits=True) -> bool:
         return self.c64 and f == 64 and W + 2 <= 64 and M >= self.c64_min_m and bits
 
-    def _c3c1_ok(self, b, nb) -> bool:
+    def _c3c1_ok(self, b, nb, M=0) -> bool:
         """Fuse block b's conv3 with block nb's conv1 (c3c1.hip): stride-1 boundaries out of a plain
         block, not into a projection block -- 64 channels wide (stage 2: conv2_block2 -> 3) and, with
         c3c1 >= 2, 128 channels wide (stage 3: conv3_block2 -> 3 and 3 -> 4; conv3_block4 feeds the
-        stride-2 grid).  (Out of a fused projection block, conv2_block1 with K = 128, it measured no
-        gain: 2.77 ms fused vs 1.87 + 0.90 ms separate at b2560, profiles/r4_c3c1.txt.)"""
-        wide = 128 if self.c3c1 >= 2 else 64
-        return (bool(self.c3c1) and nb is not None and b.filters == nb.filters and b.filters in (64, wide)
-                and not b.proj and not nb.proj and nb.stride == 1)
+        stride-2 grid).  Out of the fused stride-1 projection block (conv2_block1, the dual-source
+        conv3 + shortcut GEMM with K = 64 + 64) the dual form of the kernel takes the boundary when
+        c3c1_proj is on and the boundary's M GEMM rows reach c3c1_proj_min_m (M = 0: not asked)."""
+        if not self.c3c1 or nb is None or nb.proj or nb.stride != 1 or b.filters != nb.filters:
+            return False
+        if b.proj:
+            return (self.c3c1_proj and self.fuse_proj and b.filters == 64 and b.stride == 1 and b.cin == 64
+                    and M >= self.c3c1_proj_min_m)
+        return b.filters in (64, 128 if self.c3c1 >= 2 else 64)
 
     def _c2_wgrad(self, y1, g2, c2n, f, B, Ho, g2_n):
         """Weight gradient of a bottleneck's stride-1 3x3 conv (on the side stream when two-stream)."""
@@ -660,16 +670,19 @@ class HipEngine(SideStream):
             c3 = b.convs["3"].name
             nb = L.blocks[bi + 1] if bi + 1 < len(L.blocks) else None
             c1_done = False
-            if self._c3c1_ok(b, nb):
+            if self._c3c1_ok(b, nb, B * Ho * Ho):
                 # conv3 of this block + conv1 of the next in one launch: the next conv1 reads this
-                # block's output from LDS (c3c1.hip)
+                # block's output from LDS (c3c1.hip).  Out of the fused projection block the launch
+                # takes the block input as its second K source and the "fuse:" weight and affine.
                 an = self.acts[nb.name]
                 btn = {k: v[:B] for k, v in self.bits[nb.name].items()} if use_bits else {}
                 c1x = nb.convs["1"].name
-                k3 = self.ch[c3]
-                N.c3c1(y2, self._wf(c3, 4 * f, f), self.scale[k3:], self.shift[k3:], res, out, bt.get("out"),
+                dual = b.proj
+                k3 = self.ch["fuse:" + b.name if dual else c3]
+                w3 = self._wf("fuse:" + b.name, 4 * f, f + cin) if dual else self._wf(c3, 4 * f, f)
+                N.c3c1(y2, w3, self.scale[k3:], self.shift[k3:], res, out, bt.get("out"),
                        self._wf(c1x, nb.filters, nb.cin), self.scale[self.ch[c1x]:], self.shift[self.ch[c1x]:],
-                       an["y1"][:B], btn.get("y1"))
+                       an["y1"][:B], btn.get("y1"), **({"a2": x} if dual else {}))
                 c1_done = True
             elif b.proj and self.fuse_proj:
                 fz = "fuse:" + b.name

@@ -23,6 +23,8 @@ KEYS: Dict[str, Dict[str, str]] = {
         "c64w": "1: ... and their weight gradient",
         "c64_min_m": "GEMM rows from which the row-tile kernels run (default 262144)",
         "c3c1": "block boundaries as conv3 + next conv1 in one launch; 2 (default): stages 2-3; 1: stage 2 only; 0: off",
+        "c3c1_proj": "1: conv2_block1's conv3 + shortcut GEMM and conv2_block2's conv1 in one launch (needs c3c1 >= 1 and fuse_proj)",
+        "c3c1_proj_min_m": "GEMM rows from which it runs (default 16384: one 64-row tile per CU)",
         "c1pre": "1: next block's conv1 dgrad inside the fused conv3 backward (stage 2)",
         "proj_bwd": "1: conv2_block1's shortcut conv backward inside its fused conv3 backward (needs c1pre)",
         "proj_bwd_min_m": "GEMM rows from which it runs (default 200704: b64 at 224)",
