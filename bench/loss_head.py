@@ -1,7 +1,11 @@
 """The three loss-head kernels alone, with and without label smoothing: softmax_xent (bf16
 dlogits), softmax_xent_f32 and eval_metrics on [B][1000] fp32 logits, in microseconds per launch.
 
-    python bench/loss_head.py [--batches 32 256 1024 2560] [--smoothing 0 0.1] [--json out.json]
+    python bench/loss_head.py [--batches 32 256 1024 2560] [--smoothing 0 0.1] [--loss crossentropy bce]
+                              [--json out.json]
+
+--loss bce adds the rows of the sigmoid binary cross-entropy heads (sigmoid_bce, sigmoid_bce_f32 and
+eval_metrics(bce=True)) on the same logits, next to the softmax rows of the same build.
 
 The method of bench/eval.py: device events around 2000 back-to-back launches, three such windows,
 their median; the three windows are printed too, since their spread is what a difference between
@@ -38,6 +42,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 256, 1024, 2560])
     ap.add_argument("--smoothing", type=float, nargs="+", default=[0.0, 0.1])
+    ap.add_argument("--loss", nargs="+", choices=["crossentropy", "bce"], default=["crossentropy"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     N = require_native()
@@ -59,7 +64,13 @@ def main():
                                                                **kw),
                 "eval_metrics": lambda: N.eval_metrics(logits, lab, 1000, 5, out, **kw),
             }
-            for name, fn in calls.items():
+            bce = {
+                "sigmoid_bce": lambda: N.sigmoid_bce(logits, lab, 1000, 1.0 / B, dl16, out[0:1], out[1:2], **kw),
+                "sigmoid_bce_f32": lambda: N.sigmoid_bce_f32(logits, lab, 1000, 1.0 / B, dl32, out[0:1], out[1:2], **kw),
+                "eval_metrics(bce)": lambda: N.eval_metrics(logits, lab, 1000, 5, out, bce=True, **kw),
+            }
+            todo = [kv for loss, d in (("crossentropy", calls), ("bce", bce)) if loss in a.loss for kv in d.items()]
+            for name, fn in todo:
                 w = [timeit(fn) for _ in range(3)]
                 row = {"kernel": name, "batch": B, "smoothing": eps, "us": round(statistics.median(w), 2),
                        "windows_us": [round(x, 2) for x in w]}

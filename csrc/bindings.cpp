@@ -473,6 +473,20 @@ void softmax_xent_f32(Tensor logits, Tensor labels, int64_t ncls, double gscale,
                                f32p(correct), cur_stream(), (float)smoothing, mix_table(mix, logits.size(0))),
      "softmax_xent_f32");
 }
+// The target threshold of the sigmoid BCE heads: negative is off; no target exceeds a value >= 1.
+void check_bce_thresh(double thresh, const char* who) {
+  PCHECK(thresh == thresh && thresh < 1.0, std::string(who) + ": thresh must be < 1 (negative: off), not a NaN");
+}
+void sigmoid_bce_f32(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
+                     Tensor correct, double smoothing, OptT mix, double thresh) {
+  PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
+  PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "sigmoid_bce_f32: smoothing must be in [0, 1]");
+  check_bce_thresh(thresh, "sigmoid_bce_f32");
+  ok(pddl::sigmoid_bce_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0), (int)ncls,
+                              (float)gscale, f32p(dlogits), ld(dlogits), f32p(loss_sum), f32p(correct), cur_stream(),
+                              (float)smoothing, mix_table(mix, logits.size(0)), (float)thresh),
+     "sigmoid_bce_f32");
+}
 void prep_f32(Tensor params, Tensor table, int64_t nlayers, Tensor wf32, Tensor scale, Tensor shift, double eps) {
   PCHECK(table.is_cuda() && table.scalar_type() == torch::kUInt8, "prep table");
   PCHECK(table.numel() == nlayers * (int64_t)sizeof(pddl::PrepLayer), "prep table size");
@@ -717,14 +731,26 @@ void softmax_xent(Tensor logits, Tensor labels, int64_t ncls, double gscale, Ten
                                f32p(correct), cur_stream(), (float)smoothing, mix_table(mix, logits.size(0))),
      "softmax_xent");
 }
-void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out, double smoothing) {
+void sigmoid_bce(Tensor logits, Tensor labels, int64_t ncls, double gscale, Tensor dlogits, Tensor loss_sum,
+                 Tensor correct, double smoothing, OptT mix, double thresh) {
+  PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda(), "labels int64 GPU");
+  PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "sigmoid_bce: smoothing must be in [0, 1]");
+  check_bce_thresh(thresh, "sigmoid_bce");
+  ok(pddl::sigmoid_bce_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0), (int)ncls,
+                              (float)gscale, bfpm(dlogits), ld(dlogits), f32p(loss_sum), f32p(correct), cur_stream(),
+                              (float)smoothing, mix_table(mix, logits.size(0)), (float)thresh),
+     "sigmoid_bce");
+}
+void eval_metrics(Tensor logits, Tensor labels, int64_t ncls, int64_t k, Tensor out, double smoothing, bool bce,
+                  double thresh) {
   PCHECK(labels.scalar_type() == torch::kInt64 && labels.is_cuda() && labels.is_contiguous(), "labels int64 GPU");
   PCHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && ncls <= logits.size(1),
          "eval_metrics: logits [B][>= ncls], labels [B]");
   PCHECK(out.numel() == 3 && out.is_contiguous(), "eval_metrics: out is 3 contiguous floats");
   PCHECK(smoothing >= 0.0 && smoothing <= 1.0, "eval_metrics: smoothing must be in [0, 1]");
+  if (bce) check_bce_thresh(thresh, "eval_metrics");
   ok(pddl::eval_metrics_launch(f32p(logits), ld(logits), labels.data_ptr<int64_t>(), (int)logits.size(0), (int)ncls,
-                               (int)k, f32p(out), cur_stream(), (float)smoothing),
+                               (int)k, f32p(out), cur_stream(), (float)smoothing, bce, (float)thresh),
      "eval_metrics");
 }
 void prep(Tensor params, Tensor table, int64_t nlayers, int64_t max_elems, Tensor wbf, Tensor scale, Tensor shift,
@@ -1009,6 +1035,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_xent_f32", &softmax_xent_f32, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"),
         py::arg("gscale"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
         py::arg("mix") = py::none());
+  m.def("sigmoid_bce_f32", &sigmoid_bce_f32, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"),
+        py::arg("gscale"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
+        py::arg("mix") = py::none(), py::arg("thresh") = -1.0);
   m.def("prep_f32", &prep_f32, REL);
   m.def("wgrad_f32", &wgrad_f32, REL);
   m.def("stem_s2d", &stem_s2d, REL, py::arg("images"), py::arg("flip"), py::arg("mode"), py::arg("Hc"), py::arg("Wc"),
@@ -1045,8 +1074,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_xent", &softmax_xent, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("gscale"),
         py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
         py::arg("mix") = py::none());
+  m.def("sigmoid_bce", &sigmoid_bce, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("gscale"),
+        py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"), py::arg("smoothing") = 0.0,
+        py::arg("mix") = py::none(), py::arg("thresh") = -1.0);
   m.def("eval_metrics", &eval_metrics, REL, py::arg("logits"), py::arg("labels"), py::arg("ncls"), py::arg("k"),
-        py::arg("out"), py::arg("smoothing") = 0.0);
+        py::arg("out"), py::arg("smoothing") = 0.0, py::arg("bce") = false, py::arg("thresh") = -1.0);
   m.def("colsum_reduce", &colsum_reduce, REL);
   m.def("allow_knob_changes", [](bool on) { g_knob_tuning.store(on); }, py::arg("on") = true);
   m.def("knobs_frozen", []() { return g_launched.load() && !g_knob_tuning.load(); });

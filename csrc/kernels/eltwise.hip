@@ -965,10 +965,11 @@ __global__ void eval_metrics_kernel(const float* __restrict__ logits, int ldl, c
   }
 }
 const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k, float* out,
-                                hipStream_t s, float smoothing) {
+                                hipStream_t s, float smoothing, bool bce, float thresh) {
   if (k < 1) return "eval_metrics: k < 1";
   if (ldl < ncls) return "eval_metrics: ldl < ncls";
   if (!smoothing_ok(smoothing)) return "eval_metrics: smoothing outside [0, 1]";
+  if (bce) return eval_metrics_bce_launch(logits, ldl, labels, B, ncls, k, out, s, smoothing, thresh);   // (bce.hip)
   if (B <= 0) return nullptr;
   const float keep = 1.f - smoothing, spread = smoothing / (float)ncls;
   if (smoothing > 0.f)

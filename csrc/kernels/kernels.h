@@ -262,6 +262,16 @@ struct StemParams {
 //   6      w_lab (float bits): weight of image b's own label
 //   7      0 (reserved)
 // The identity row {b, 0, 0, 0, 0, 1.f, 1.f, 0} gives the unmixed result bit for bit.
+// Sigmoid binary cross-entropy (bce.hip; TorchEngine and the tests evaluate the same definition), K = ncls:
+//   target  the row of the softmax heads: T(y) = keep onehot(y) + spread with keep = 1 - eps, spread = eps/K;
+//           under a mix table t = w T(y_b) + (1 - w) T(y_p), w = w_lab, p = the partner.  A row has four
+//           distinct target values (none / own / partner / both); a threshold thresh >= 0 (timm's
+//           bce_target_thresh) turns each of those row constants into (value > thresh ? 1 : 0); thresh < 0: off.
+//   loss    l_j = max(z_j, 0) - t_j z_j + log1p(exp(-|z_j|)); the row's loss is (1/K) sum_j l_j (the mean over
+//           classes of Keras BinaryCrossentropy(from_logits=True) and timm), added to loss_sum.
+//   dlogits (sigma(z_j) - t_j) g for j < K with g = fl(gscale / K); columns [K, ldd) are written as zero.
+//           sigma comes from the same e = exp(-|z|): z >= 0 ? 1/(1 + e) : e/(1 + e).
+//   correct += (first argmax == counted label); under a mix table the label of the larger weight, own on a tie.
 // Preprocess + ZeroPadding2D(3) + 2x2 space-to-depth: channel (dy*2+dx)*4 + c of pixel (i, j)
 // is the padded preprocessed pixel (2i+dy-3, 2j+dx-3, c) (c = 3 is zero).  The 7x7/s2 stem
 // conv then becomes a 4x4/s1 "window" implicit GEMM with K = 4*4*16 = 256.
@@ -385,8 +395,24 @@ const char* softmax_xent_launch(const float* logits, int ldl, const int64_t* lab
 // Evaluation head (no dlogits): out[0] += loss sum, out[1] += top-1 hits, out[2] += top-k hits.
 // (smoothing: the label-smoothing eps in [0, 1] of all three loss heads; the target is
 // (1 - eps)*onehot + eps/ncls, and 0 is the plain one-hot cross-entropy)
+// (bce: the loss of the sigmoid binary cross-entropy head below instead, with its thresh; the hits are the same)
 const char* eval_metrics_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k,
-                                float* out, hipStream_t s, float smoothing = 0.f);
+                                float* out, hipStream_t s, float smoothing = 0.f, bool bce = false,
+                                float thresh = -1.f);
+// The sigmoid binary cross-entropy training head (bce.hip; the definition is at the mix table above): the
+// arguments of softmax_xent_launch and the target threshold (negative: off; a NaN or a value >= 1, above
+// which no target lies, is an error), one streaming pass per row.  eval_metrics_bce_launch is what
+// eval_metrics_launch(bce = true) forwards to.
+const char* sigmoid_bce_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
+                               float gscale, uint16_t* dlogits, int ldd, float* loss_sum, float* correct,
+                               hipStream_t s, float smoothing = 0.f, const int32_t* mix = nullptr,
+                               float thresh = -1.f);
+const char* sigmoid_bce_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls,
+                               float gscale, float* dlogits, int ldd, float* loss_sum, float* correct,
+                               hipStream_t s, float smoothing = 0.f, const int32_t* mix = nullptr,
+                               float thresh = -1.f);
+const char* eval_metrics_bce_launch(const float* logits, int ldl, const int64_t* labels, int B, int ncls, int k,
+                                    float* out, hipStream_t s, float smoothing, float thresh);
 
 // Per-layer parameter preparation after every optimizer step (one launch for all layers).
 struct PrepLayer {

@@ -27,7 +27,8 @@ def _banner(cfg, strategy):
           f"mixup={cfg.mixup:g}, cutmix={cfg.cutmix:g}, mix_prob={cfg.mix_prob:g}, "
           f"rrc={cfg.rrc}, rrc_scale={cfg.rrc_scale[0]:g}-{cfg.rrc_scale[1]:g}, "
           f"rrc_ratio={cfg.rrc_ratio[0]:g}-{cfg.rrc_ratio[1]:g}, antialias={cfg.antialias}, "
-          f"randaugment={tuple(cfg.randaugment) if cfg.randaugment else None}", flush=True)
+          f"randaugment={tuple(cfg.randaugment) if cfg.randaugment else None}, "
+          f"loss={cfg.loss}, bce_threshold={cfg.bce_threshold}", flush=True)
 
 
 def model_summary(cfg) -> str:
@@ -156,7 +157,7 @@ def _evaluate(cfg, strategy, trainer) -> int:
         if cfg.metrics_jsonl:
             rec = {"evaluate": True, **m, "images_per_sec": m["images"] / dt,
                    "replicas": strategy.num_replicas_in_sync, "label_smoothing": cfg.label_smoothing,
-                   "antialias": bool(cfg.antialias)}
+                   "antialias": bool(cfg.antialias), "loss_head": cfg.loss, "bce_threshold": cfg.bce_threshold}
             with open(cfg.metrics_jsonl, "a") as f:
                 f.write(json.dumps(rec) + "\n")
     _leave_process_group()

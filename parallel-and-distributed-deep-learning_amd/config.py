@@ -54,6 +54,9 @@ class TrainConfig:
     label_smoothing: float = 0.0                   # eps of the loss target (1 - eps) * onehot + eps / num_classes
                                                    # (Keras CategoricalCrossentropy(label_smoothing)); training,
                                                    # validation and --evaluate all report this loss
+    loss: str = "crossentropy"                     # additive: "bce" = per-class sigmoid binary cross-entropy against
+                                                   # the same (smoothed, mixed) target row, mean over the classes
+    bce_threshold: Optional[float] = None          # loss = bce: targets become (value > T ? 1 : 0); None = off
     mixup: float = 0.0                             # additive: mixup alpha (lambda ~ Beta(alpha, alpha)); 0 = off
     cutmix: float = 0.0                            # additive: CutMix alpha; 0 = off (both on: one of the two per batch)
     mix_prob: float = 1.0                          # probability that a training batch is mixed at all
@@ -167,10 +170,19 @@ def check_accum(cfg: TrainConfig) -> None:
 
 def check_loss(cfg: TrainConfig) -> None:
     """--label-smoothing eps: a value outside [0, 1] is a configuration error, raised before
-    anything is built."""
+    anything is built.  Likewise an unknown --loss, a --bce-target-threshold outside [0, 1) and a
+    threshold without --loss bce."""
     eps = cfg.label_smoothing
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps <= 1.0:
         raise ValueError(f"--label-smoothing must be a number in [0, 1] (got {eps!r})")
+    loss, thr = getattr(cfg, "loss", "crossentropy"), getattr(cfg, "bce_threshold", None)
+    if loss not in ("crossentropy", "bce"):
+        raise ValueError(f"--loss must be crossentropy or bce (got {loss!r})")
+    if thr is not None:
+        if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 <= thr < 1.0:
+            raise ValueError(f"--bce-target-threshold must be a number in [0, 1) (got {thr!r})")
+        if loss != "bce":
+            raise ValueError("--bce-target-threshold needs --loss bce: the softmax cross-entropy takes the soft target")
 
 
 def check_mix(cfg: TrainConfig) -> None:
@@ -262,6 +274,13 @@ def add_cli_args(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--label-smoothing", type=float, dest="label_smoothing",
       help="eps in [0, 1]: the loss target is (1 - eps) * onehot + eps / num_classes (0.1 in the large-batch "
            "recipes); loss, val_loss and --evaluate all report the smoothed loss")
+    a("--loss", metavar="{crossentropy,bce}",
+      help="bce: the per-class sigmoid binary cross-entropy of the ResNet-strikes-back / timm recipes against the "
+           "same (smoothed, mixed) target, averaged over the classes, as one fused head kernel; loss, val_loss and "
+           "--evaluate all report it (default crossentropy: softmax)")
+    a("--bce-target-threshold", type=float, dest="bce_threshold", metavar="T",
+      help="with --loss bce: every target value becomes 1 if it exceeds T in [0, 1) and 0 otherwise (timm's "
+           "bce_target_thresh; 0.2 in recipe A1)")
     a("--mixup", type=float, metavar="ALPHA",
       help="mixup: each training batch is blended with a permutation of itself, lambda ~ Beta(ALPHA, ALPHA), inside "
            "the preprocess kernel, and the loss takes the matching soft target (0 = off; 0.2 in the usual recipes)")

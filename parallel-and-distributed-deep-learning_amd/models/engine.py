@@ -30,7 +30,7 @@ import torch
 from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
-from .resnet50 import BN_EPS, ParamLayout, check_label_smoothing
+from .resnet50 import BN_EPS, ParamLayout, check_label_smoothing, check_loss_head, head_kwargs
 from .side_stream import SideStream
 
 _PREP_FMT = "<6i2q8i"
@@ -113,7 +113,7 @@ class HipEngine(SideStream):
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: int = 224,
                  device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, bitmask: Optional[bool] = None,
                  grad_ring: Optional[int] = None, graphed=False, label_smoothing: float = 0.0,
-                 antialias: bool = False):
+                 antialias: bool = False, loss: str = "crossentropy", bce_threshold: Optional[float] = None):
         # antialias: box tables are resampled by the triangle-filter stem kernel (a launch constant, like
         # label_smoothing), and evaluation at image_size > crop goes through it with aa_full
         self.antialias = bool(antialias)
@@ -121,6 +121,10 @@ class HipEngine(SideStream):
         # the loss of forward_backward, evaluate and evaluate_topk alike; a launch constant of the
         # head kernels, so a captured step keeps the value it was captured with
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        # loss "bce": the sigmoid binary cross-entropy head (sigmoid_bce, eval_metrics(bce=True)) in
+        # place of softmax_xent, likewise everywhere and a launch constant; the default adds nothing to a call
+        self.loss, self.bce_threshold = check_loss_head(loss, bce_threshold)
+        self._head_kw, self._eval_kw = head_kwargs(self.loss, self.bce_threshold)
         self._grad_ring = grad_ring   # None: GRAD_RING_SMALL at batches <= 64, else GRAD_RING
         # graphed: steps replay from HIP graphs -- True: one stream (see TWO_STREAM_MAX_BATCH);
         # "segmented": bucket-segmented graphs (train/graph.py SegmentedStepGraphs) with the weight
@@ -731,6 +735,11 @@ class HipEngine(SideStream):
             return self.TWO_STREAM_OK and ts == "1"
         return self.TWO_STREAM_OK and batch <= self.TWO_STREAM_MAX_BATCH and (not self.graphed or self.defer_side)
 
+    @property
+    def _head(self):
+        """The training head of the engine's loss: softmax_xent, or sigmoid_bce (same arguments + thresh)."""
+        return self.N.sigmoid_bce if self.loss == "bce" else self.N.softmax_xent
+
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
                          bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
@@ -748,8 +757,8 @@ class HipEngine(SideStream):
         prof.push("step/backward")
         logits = self.logits[:B]
         dl = self.dlogits[:B]
-        N.softmax_xent(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                       self.label_smoothing, **_mix_kw(mix))
+        self._head(logits, lab, self.num_classes, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                   self.label_smoothing, **_mix_kw(mix), **self._head_kw)
         if self._dgrad_ready is not None:   # the dgrad weights after_update prepared on the side stream
             if not torch.cuda.is_current_stream_capturing():   # (a capture starts synchronized)
                 torch.cuda.current_stream(self.device).wait_event(self._dgrad_ready)
@@ -947,8 +956,8 @@ class HipEngine(SideStream):
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
         N = self.N
-        N.softmax_xent(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
-                       self.stats[1:2], self.label_smoothing)
+        self._head(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
+                   self.stats[1:2], self.label_smoothing, **self._head_kw)
         return self.stats
 
     @torch.no_grad()
@@ -959,7 +968,8 @@ class HipEngine(SideStream):
         self.eval_stats.zero_()
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
-        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing)
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing,
+                            **self._eval_kw)
         return self.eval_stats
 
 

@@ -30,7 +30,7 @@ from ..ops.native import require_native
 from ..utils import profiling as prof
 from ..utils.envopts import opt
 from .engine import _BNG_FMT, _CRED_FMT, _FIN_FMT, _PREP_FMT, STEM_K, _mix_kw, _rrc_kw, eval_boxes
-from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
+from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing, check_loss_head, head_kwargs
 from .side_stream import SideStream
 
 
@@ -48,8 +48,10 @@ class HipF32Engine(SideStream):
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
                  device="cuda", bn_mode: str = "frozen", num_classes: int = 1000, label_smoothing: float = 0.0,
-                 antialias: bool = False):
+                 antialias: bool = False, loss: str = "crossentropy", bce_threshold: Optional[float] = None):
         self.label_smoothing = check_label_smoothing(label_smoothing)   # the loss of every head call
+        self.loss, self.bce_threshold = check_loss_head(loss, bce_threshold)   # "bce": sigmoid_bce_f32 in its place
+        self._head_kw, self._eval_kw = head_kwargs(self.loss, self.bce_threshold)
         self.antialias = bool(antialias)                                 # (HipEngine.__init__: the same two fields)
         self.aa_full = eval_boxes(antialias, batch, crop, image_size if image_size is not None else crop, device)
         if bn_mode not in self.BN_MODES:
@@ -308,6 +310,11 @@ class HipF32Engine(SideStream):
         lab.copy_(labels, non_blocking=True)
         return lab
 
+    @property
+    def _head(self):
+        """The training head of the engine's loss: softmax_xent_f32, or sigmoid_bce_f32 (same arguments + thresh)."""
+        return self.N.sigmoid_bce_f32 if self.loss == "bce" else self.N.softmax_xent_f32
+
     # ------------------------------------------------------------------ train step
     def forward_backward(self, images, labels, gscale, flip=None, crop_offset=(0, 0),
                          bucket_cb: Optional[Callable[[int], None]] = None, buckets=None, mix=None, rrc=None):
@@ -322,8 +329,8 @@ class HipF32Engine(SideStream):
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
-        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                           self.label_smoothing, **_mix_kw(mix))
+        self._head(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                   self.label_smoothing, **_mix_kw(mix), **self._head_kw)
         bks = buckets if buckets is not None else []
         nb = [0]
 
@@ -443,8 +450,8 @@ class HipF32Engine(SideStream):
         self.stats.zero_()
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
-        self.N.softmax_xent_f32(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
-                                self.stats[1:2], self.label_smoothing)
+        self._head(self.logits[:B], lab, self.num_classes, 0.0, self.dlogits[:B], self.stats[0:1],
+                   self.stats[1:2], self.label_smoothing, **self._head_kw)
         return self.stats
 
     @torch.no_grad()
@@ -455,7 +462,8 @@ class HipF32Engine(SideStream):
         self.eval_stats.zero_()
         lab = self._labels(labels, B)
         self._forward(images, B, False, None, (0, 0))
-        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing)
+        self.N.eval_metrics(self.logits[:B], lab, self.num_classes, int(k), self.eval_stats, self.label_smoothing,
+                            **self._eval_kw)
         return self.eval_stats
 
 
@@ -486,9 +494,10 @@ class HipF32EngineBNTrain(HipF32Engine):
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, image_size: Optional[int] = None,
                  device="cuda", bn_mode: str = "train", num_classes: int = 1000, label_smoothing: float = 0.0,
-                 antialias: bool = False):
+                 antialias: bool = False, loss: str = "crossentropy", bce_threshold: Optional[float] = None):
         super().__init__(layout, batch, crop=crop, image_size=image_size, device=device, bn_mode=bn_mode,
-                         num_classes=num_classes, label_smoothing=label_smoothing, antialias=antialias)
+                         num_classes=num_classes, label_smoothing=label_smoothing, antialias=antialias, loss=loss,
+                         bce_threshold=bce_threshold)
         assert struct.calcsize(_STAT_FMT) == self.N.BNSTAT_LAYER_BYTES
         f32 = dict(dtype=torch.float32, device=self.device)
         n = self.nch
@@ -649,8 +658,8 @@ class HipF32EngineBNTrain(HipF32Engine):
         prof.push("step/backward")
         ncls = self.num_classes
         dl = self.dlogits[:B]
-        N.softmax_xent_f32(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
-                           self.label_smoothing, **_mix_kw(mix))
+        self._head(self.logits[:B], lab, ncls, float(gscale), dl, self.stats[0:1], self.stats[1:2],
+                   self.label_smoothing, **_mix_kw(mix), **self._head_kw)
         bks = buckets if buckets is not None else []
         nb = [0]
 

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing
+from .resnet50 import BN_EPS, BN_MOMENTUM, ParamLayout, check_label_smoothing, check_loss_head
 
 
 def mix_rows(mix: torch.Tensor, B: int, H: int, W: int):
@@ -51,6 +51,27 @@ def mix_targets(labels: torch.Tensor, mix: torch.Tensor, num_classes: int, label
     T = F.one_hot(labels, num_classes).float() * (1.0 - label_smoothing) + label_smoothing / num_classes
     w = w_lab.view(B, 1)
     return w * T + (1.0 - w) * T[partner], torch.where(w_lab >= 0.5, labels, labels[partner])
+
+
+def bce_targets(labels: torch.Tensor, mix, num_classes: int, label_smoothing: float = 0.0, threshold=None):
+    """(targets [B][ncls], counted labels [B]) of the sigmoid binary cross-entropy head: the (smoothed,
+    mixed) target row of the softmax head, every value of which becomes (value > threshold ? 1 : 0)
+    under a threshold."""
+    if mix is None:
+        t = F.one_hot(labels, num_classes).float() * (1.0 - label_smoothing) + label_smoothing / num_classes
+        counted = labels
+    else:
+        t, counted = mix_targets(labels, mix, num_classes, label_smoothing)
+    if threshold is not None:
+        t = (t > threshold).to(t.dtype)
+    return t, counted
+
+
+def sigmoid_bce_sum(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """sum over rows of (1/K) sum_j max(z, 0) - t z + log1p(exp(-|z|)) (the definition in
+    csrc/kernels/kernels.h; its gradient is (sigmoid(z) - t) / K)."""
+    per = logits.clamp_min(0) - target * logits + torch.log1p(torch.exp(-logits.abs()))
+    return per.mean(1).sum()
 
 
 def rrc_taps(o: torch.Tensor, n: torch.Tensor, N: int):
@@ -401,10 +422,12 @@ class TorchEngine:
 
     def __init__(self, layout: ParamLayout, batch: int, crop: int = 224, device="cpu", bn_mode="frozen",
                  num_classes: int = 1000, bf16_points: bool = False, fused_proj: bool = False,
-                 label_smoothing: float = 0.0, antialias: bool = False):
+                 label_smoothing: float = 0.0, antialias: bool = False, loss: str = "crossentropy",
+                 bce_threshold: Optional[float] = None):
         self.L = layout
         self.antialias = bool(antialias)
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.loss, self.bce_threshold = check_loss_head(loss, bce_threshold)
         self.device = torch.device(device)
         self.batch = batch
         self.crop = crop
@@ -432,11 +455,14 @@ class TorchEngine:
         x = preprocess(images.to(self.device), self.crop, True, flip, crop_offset, mix, rrc, self.antialias)
         logits = self.model.logits(p, x, training=True)
         lab = counted = labels.to(self.device)
-        if mix is not None:
+        if mix is not None and self.loss != "bce":
             target, counted = mix_targets(lab, mix, logits.shape[1], self.label_smoothing)
             if bool((mix_rows(mix, lab.shape[0], 0, 0)[3] == 1.0).all()):
                 mix = None     # every label keeps weight 1 (the identity table): the integer-label loss, bit for bit
-        if mix is None:
+        if self.loss == "bce":     # per-class sigmoid cross-entropy against the same target row
+            target, counted = bce_targets(lab, mix, logits.shape[1], self.label_smoothing, self.bce_threshold)
+            loss_sum = sigmoid_bce_sum(logits, target)
+        elif mix is None:
             loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
         else:      # the soft target between each label and its partner's (smoothing is inside it)
             loss_sum = F.cross_entropy(logits, target, reduction="sum")
@@ -450,13 +476,19 @@ class TorchEngine:
                 bucket_cb(i)
         return stats
 
+    def _eval_loss(self, logits, lab):
+        if self.loss == "bce":
+            return sigmoid_bce_sum(logits, bce_targets(lab, None, logits.shape[1], self.label_smoothing,
+                                                       self.bce_threshold)[0])
+        return F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
+
     @torch.no_grad()
     def evaluate(self, images, labels):
         x = preprocess(images.to(self.device), self.crop, False, antialias=self.antialias)
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
+        loss_sum = self._eval_loss(logits, lab)
         return torch.stack([loss_sum, (logits.argmax(1) == lab).sum().float()])
 
     @torch.no_grad()
@@ -468,7 +500,7 @@ class TorchEngine:
         self.model.stats = self.params
         logits = self.model.logits(self.params, x, training=False)
         lab = labels.to(self.device)
-        loss_sum = F.cross_entropy(logits, lab, reduction="sum", label_smoothing=self.label_smoothing)
+        loss_sum = self._eval_loss(logits, lab)
         vl = logits.gather(1, lab[:, None])
         idx = torch.arange(logits.shape[1], device=logits.device)[None, :]
         rank = ((logits > vl) | ((logits == vl) & (idx < lab[:, None]))).sum(1)

@@ -201,3 +201,32 @@ def check_label_smoothing(eps) -> float:
     if not 0.0 <= eps <= 1.0:
         raise ValueError(f"label_smoothing must be in [0, 1], got {eps}")
     return eps
+
+
+LOSSES = ("crossentropy", "bce")
+
+
+def check_loss_head(loss, bce_threshold=None):
+    """(loss, bce_threshold) of a loss head, checked (ValueError otherwise).  "crossentropy": the
+    softmax cross-entropy; "bce": the per-class sigmoid binary cross-entropy against the same
+    (smoothed, mixed) target row, averaged over the classes.  bce_threshold (None: off; "bce" only;
+    timm's bce_target_thresh) in [0, 1): every target value becomes (value > threshold ? 1 : 0)."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    if bce_threshold is None:
+        return loss, None
+    if loss != "bce":
+        raise ValueError("bce_threshold needs loss='bce'")
+    thr = float(bce_threshold)
+    if not 0.0 <= thr < 1.0:
+        raise ValueError(f"bce_threshold must be in [0, 1), got {bce_threshold}")
+    return loss, thr
+
+
+def head_kwargs(loss, bce_threshold):
+    """What a HIP engine adds to its head calls for the loss: (training-head keywords, eval_metrics
+    keywords); both empty for the softmax cross-entropy, whose calls stay as they are."""
+    if loss != "bce":
+        return {}, {}
+    thr = -1.0 if bce_threshold is None else float(bce_threshold)
+    return {"thresh": thr}, {"bce": True, "thresh": thr}

@@ -83,6 +83,8 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
     one stream (HipEngine.TWO_STREAM_MAX_BATCH); "segmented": bucket-segmented graphs whose
     weight gradients replay as a side graph per segment (HipEngine._side_run)."""
     L = ParamLayout(cfg.num_classes)
+    # --loss / --bce-target-threshold: launch constants of every engine's head, like label_smoothing
+    loss = dict(loss=getattr(cfg, "loss", "crossentropy"), bce_threshold=getattr(cfg, "bce_threshold", None))
     if device.type == "cuda" and cfg.precision == "bf16":
         from ..models.engine import HipEngine, make_hip_engine
         if graphed is None:
@@ -90,16 +92,16 @@ def build_engine(cfg, device: torch.device, cap: int, graphed=None):
         return make_hip_engine(L, cap, bn_mode=cfg.bn_mode, crop=cfg.crop, image_size=cfg.image_size,
                                device=device, num_classes=cfg.num_classes,
                                grad_ring=HipEngine.GRAD_RING if graphed else None, graphed=graphed,
-                               label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
+                               label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False), **loss)
     if device.type == "cuda":
         from ..models.engine_f32 import HipF32Engine, HipF32EngineBNTrain
         # frozen: the reference's configuration; train: batch statistics (both explicit fp32 schedules)
         cls = HipF32Engine if cfg.bn_mode == "frozen" else HipF32EngineBNTrain
         return cls(L, cap, crop=cfg.crop, image_size=cfg.image_size, device=device, num_classes=cfg.num_classes,
-                   label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
+                   label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False), **loss)
     from ..models.reference import TorchEngine
     return TorchEngine(L, cap, crop=cfg.crop, device=device, bn_mode=cfg.bn_mode, num_classes=cfg.num_classes,
-                       label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False))
+                       label_smoothing=cfg.label_smoothing, antialias=getattr(cfg, "antialias", False), **loss)
 
 
 class Augment:

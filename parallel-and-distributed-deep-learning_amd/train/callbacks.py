@@ -238,6 +238,10 @@ class JsonlLogger(Callback):
         rec["rrc_scale"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_scale", (0.08, 1.0))]
         rec["rrc_ratio"] = [float(v) for v in getattr(self.trainer.cfg, "rrc_ratio", (3 / 4, 4 / 3))]
         rec["antialias"] = bool(getattr(self.trainer.cfg, "antialias", False))
+        # (`loss` is taken by the value: the kind of loss is `loss_head`; a bce run's loss and val_loss
+        # compare with other bce runs only)
+        rec["loss_head"] = str(getattr(self.trainer.cfg, "loss", "crossentropy"))
+        rec["bce_threshold"] = getattr(self.trainer.cfg, "bce_threshold", None)
         if "images_per_sec" in rec and self.baseline_ips:
             rec["baseline_ips"] = float(self.baseline_ips)
             rec["scaling_efficiency"] = efficiency(rec["images_per_sec"], n, self.baseline_ips)
